@@ -5,7 +5,14 @@ classify launch, plus the rule_stats group-by for tables over 4096 rules) over o
 resident in HBM.  The default output mode is emit (include/upe_gpu.h): verdicts plus one 16-byte
 rewritten-header record per packet, frames read only; --mode inplace rewrites the frames in place
 as upe_gpu_process does, and the JSON line carries the other mode's rate too ("other_mode").  At N=1 the workload is BASELINE.json configs[1] (config B: 1M x 64 B UDP/IPv4, 8 rules);
---config A / C / D run the other configurations.  A config-B run also times the IMIX workload
+--config A / C / D run the other configurations.
+
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what `value` needs: it
+sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs DIR is
+given (dump_outputs below) and prints the line.  Everything else this file measures runs only
+with --full, after the timed region, and never changes `value`.
+
+A --full config-B run also times the IMIX workload
 (config C) after the main region, on every rank, and reports it as "imix" (not `value`), so that
 the 64 B and IMIX rates come out of the same run at each GPU count.  Every step gets its own pristine copy of the
 batch (the path rewrites TTL / checksum / MACs in place, so re-running a batch would change the
@@ -15,9 +22,9 @@ Multi-GPU (`python bench.py --gpus N`, which starts the N ranks under torch.dist
 itself, or the same launcher run by the caller): one process per GPU, each with its own static
 shard of the packet stream (a full config-B batch per step, tables replicated), no data-path
 collective — weak scaling.  torch.distributed carries only the barrier and the max-over-ranks
-time.  The CPU baseline is timed by rank 0 after the timed regions at every N.
+time.  With --full the CPU baseline is timed by rank 0 after the timed regions at every N.
 
-After the timed region (never part of `value`): the other output mode, the IMIX leg, the ring
+With --full, after the timed region (never part of `value`): the other output mode, the IMIX leg, the ring
 leg (16 resident batches per launch), the achievable-bandwidth probe, and the host-inclusive legs
 — the DMA round trip (upe_gpu_process_host[_emit]: pinned hipMemcpyAsync in and out) and the mapped
 path (upe_gpu_process_mapped[_emit]: the kernel reads and writes the pinned host batch over the
@@ -28,7 +35,7 @@ Prints ONE JSON line (rank 0).  roofline.achieved = algorithmic bytes per launch
 §8(d): B(p) = 8 + E(p) + 4 + W(p)) / the mean launch duration, measured with HIP events on the
 launch stream over the timed region (each sample's event pair brackets EVENT_SPAN consecutive
 launches); roofline.traffic = HBM bytes per launch from the committed PMC passes
-(profiles/pmc_config<X>.json).  cpu_baseline = the reference
+(profiles/pmc_config<X>.json).  cpu_baseline (--full) = the reference
 src/worker.c (oracle/_ref, built from the reference sources) timed on this host's cores over a
 bounded sample of the same workload.
 """
@@ -795,6 +802,55 @@ def ring_leg(torch, dev, dist, wl, worker, count: int, launches: int) -> dict:
                     "not value (value = one launch per batch)"}
 
 
+DUMP_PACKETS = {"emit": 1 << 20, "inplace": 1 << 18}   # most packets a dump holds (under 64 MB)
+
+
+def dump_outputs(torch, path: str, rank: int, mode: str, wl, verdict: np.ndarray, hdr,
+                 last_frames) -> dict:
+    """--dump-outputs: what the last timed step handed back, as `path`/<name>.npy (rank r > 0:
+    <name>_rank<r>.npy), so that two builds run with the same arguments (the workload is seeded:
+    the same inputs every run) can be compared output for output.
+
+      verdict   (k,) float64: the step's uint32 verdict words (exact in float64)
+      records   emit mode, (k, 4) float64: each packet's 16-byte rewritten-header record as four
+                little-endian uint32 words, zero for a packet that is not forwarded — the records
+                as a caller walks them out of the per-group layout (gpu.expand_records), so the
+                slots the kernel leaves unwritten never reach the file
+      frames    inplace mode, (k, REWRITE_EXTENT) float32: the first bytes of each frame of the
+                step's batch as the step left them (only those can change), zero past its length
+      packets   only when the batch has more packets than a dump holds (DUMP_PACKETS): the sorted
+                packet indices of the k rows, a fixed seeded sample
+
+    `hdr`: the device tensor of emit-mode records; `last_frames`: the device bytes of the batch
+    copy the last step processed.  Returns {name: shape}."""
+    from upe_amd import gpu
+    from upe_amd.layout import REWRITE_EXTENT, desc_lens, desc_offsets
+
+    n = len(verdict)
+    cap = DUMP_PACKETS[mode]
+    pick = (np.sort(np.random.default_rng(12345).choice(n, cap, replace=False)) if n > cap
+            else None)
+    arrays = {"verdict": verdict.astype(np.float64)}
+    if mode == "emit":
+        rec = gpu.expand_records(hdr.cpu().numpy(), verdict)
+        arrays["records"] = rec.view("<u4").astype(np.float64)
+    else:
+        offs, lens = desc_offsets(wl.desc).astype(np.int64), desc_lens(wl.desc).astype(np.int64)
+        if pick is not None:
+            offs, lens = offs[pick], lens[pick]
+        col = np.arange(REWRITE_EXTENT, dtype=np.int64)
+        at = np.minimum(offs[:, None] + col, last_frames.numel() - 1)
+        head = last_frames[torch.from_numpy(at).to(last_frames.device)].cpu().numpy()
+        arrays["frames"] = np.where(col < lens[:, None], head, 0).astype(np.float32)
+    if pick is not None:
+        arrays = {k: (a if k == "frames" else a[pick]) for k, a in arrays.items()}
+        arrays["packets"] = pick.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def line_summary(out: dict) -> dict:
     """The line's headline figures in one small object, printed last (a reader that keeps only the
     tail of a long line still sees them): per leg Mpps, kernel time, roofline fraction and
@@ -885,7 +941,9 @@ def launch_ranks(gpus: int, argv: list) -> int:
     return subprocess.run(launch_cmd(gpus, argv, port), cwd=ROOT).returncode
 
 
-def main() -> None:
+def parse_args(argv=None):
+    """The command line.  Without --full every leg beside `value` is switched off here, whatever
+    the options that tune those legs say."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
                     help="GPUs (ranks) of this node; N > 1 without a launcher starts N ranks "
@@ -943,7 +1001,25 @@ def main() -> None:
                          "runs; 0 skips it)")
     ap.add_argument("--ring", type=int, default=16,
                     help="batches per launch of the ring leg (config B; 0 skips it)")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside value after the timed region (other output "
+                         "mode, IMIX, strong scaling, egress, ring, bandwidth probe, config D, "
+                         "host legs, workers sharing the GPU, CPU baseline and drop-in pipeline); "
+                         "the options that tune or skip those legs act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to "
+                         "DIR/<name>.npy (dump_outputs)")
+    args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run sets up, warms up, times the steps and prints the line: no other leg
+        args.no_other_mode = args.no_imix = args.no_hbm_probe = args.no_cpu_baseline = True
+        args.strong = args.ring = args.config_d_steps = args.host_reps = 0
+        args.workers_per_gpu = 0
+    return args
+
+
+def main() -> None:
+    args = parse_args()
     if args.gpus is not None and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     world = world_check(args.gpus, os.environ)
@@ -1071,6 +1147,12 @@ def main() -> None:
     v_first = verdict.cpu().numpy().view(np.uint32).copy()
     classify_ms, finalize_ms, launches = worker.timing_read()
     worker.timing_enable(False)
+    # the last timed step's outputs, written before any later leg reuses the buffers
+    dumped = None
+    if args.dump_outputs:
+        c_last = (args.warmup + args.steps - 1) % copies
+        dumped = dump_outputs(torch, args.dump_outputs, rank, args.mode, wl, v_first, hdr,
+                              pool[c_last * stride: c_last * stride + fbytes])
     # the other output mode over the same number of steps (after the timed region; each step
     # again on its own batch copy), so the line shows both: emit <-> in-place rewrite
     other = None
@@ -1108,7 +1190,8 @@ def main() -> None:
         strong = {k: strong_leg(torch, dev, dist, rank, world, local, k, args.steps, args.warmup)
                   for k in ("B", "C")}
     egress = None
-    if args.config == "B" and args.mode == "emit" and not args.packets and rank == 0:
+    if (args.full and args.config == "B" and args.mode == "emit" and not args.packets
+            and rank == 0):
         egress = egress_leg(torch, dev, wl, worker, pool, stride, copies, desc)
     ring = None
     if args.config == "B" and args.ring > 0 and not args.packets:
@@ -1218,6 +1301,8 @@ def main() -> None:
                         "batches (src/rule_table.c:163-176) / wall time",
             },
         }
+        if dumped:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if other:
             out["other_mode"] = other
         if imix:

@@ -98,15 +98,15 @@ def test_two_rank_static_shards_on_gpu(case, emit):
 
 
 def test_bench_two_ranks():
-    """bench.py's N > 1 path end to end, started the way the driver starts N = 1: plain
-    `python bench.py --gpus 2`, which launches its two ranks itself (here on the one GPU, gloo
+    """bench.py's N > 1 path end to end, started the way the driver starts N = 1:
+    `python bench.py --gpus 2 --full`, which launches its two ranks itself (here on the one GPU, gloo
     for the barrier and the max / sum over ranks, as UPE_BENCH_DIST_BACKEND allows on a one-GPU
     box): config B plus the IMIX leg, each rank its own shard (weak scaling), the strong-scaling
     leg (one B and one C batch split into the two ranks' contiguous shards) and rank 0's CPU
     baseline after the timed regions."""
     env = dict(os.environ, UPE_BENCH_DIST_BACKEND="gloo", OMP_NUM_THREADS="4")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, "bench.py", "--gpus", "2",
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--full",
            "--steps", "20", "--warmup", "5", "--no-hbm-probe", "--cpu-threads", "2",
            "--dropin-seconds", "0", "--max-copies", "24", "--imix-copies", "8",
            "--imix-v6fwd", "0"]

@@ -1,6 +1,6 @@
 """Split a rocprofv3 kernel trace of one bench.py run into its legs and summarise each.
 
-A default config-B bench run launches the same classify instantiation for two workloads: the
+A config-B `bench.py --full` run launches the same classify instantiation for two workloads: the
 64 B batches of `value` and, after the other-mode leg, the IMIX batches of the "imix" field.
 rocprofv3's --stats table averages them together; this splits the dispatches of each kernel
 into legs at gaps longer than --gap-ms (the IMIX leg starts after its batch is generated on the
