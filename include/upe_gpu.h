@@ -543,10 +543,57 @@ int upe_gpu_process_queue_emit(upe_gpu_ctx_t *ctx, const upe_gpu_batch_t *batche
 /* upe_gpu_process() plus software RSS in the same pass (reference src/rx_pcap.c:67-77 parses
  * every packet a second time on the RX thread for this): d_flow_hash[i] (device, n uint32) =
  * flow_hash() of the packet's flow key (src/parser.c:113-135) when parse_flow_key succeeds, 0
- * otherwise (verdict code DROP_PARSE or CONSUMED says which).  A caller spreading a capture over
- * workers takes hash & (workers - 1), as the reference's RX thread does. */
+ * otherwise (verdict code DROP_PARSE or CONSUMED says which; a parsed packet can hash to 0 too).
+ * The hash alone does not give the worker ring: the RX thread sends a packet that parses to ring
+ * hash & (rings - 1) and every other packet to the ring its round-robin cursor names
+ * (src/rx_pcap.c:19-25,74-77).  upe_gpu_rx_dispatch below makes that choice, and it runs before
+ * any worker has classified (and rewritten) the frames. */
 int upe_gpu_process_rss(upe_gpu_ctx_t *ctx, uint8_t *d_frames, const uint64_t *d_desc,
                         uint32_t *d_verdict, uint32_t *d_flow_hash, size_t n, void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* RX dispatch: spreading a batch over the worker rings                                        */
+/* ------------------------------------------------------------------------------------------ */
+/* The RX thread's ring choice (reference src/rx_pcap.c:19-25,67-80) for a batch resident in GPU
+ * memory ("Batch layout", the UPE_FRAME_TAIL rule of upe_gpu_process), `rings` a power of two up
+ * to UPE_RX_RINGS_MAX: a packet whose parse_flow_key succeeds (src/parser.c:6-111) goes to ring
+ * flow_hash & (rings - 1) (src/parser.c:113-135); every other packet — ARP and ICMPv6 NS/NA
+ * among them, the RX thread does not call handle_control_packet — goes to the ring named by the
+ * round-robin cursor, which then steps: the k-th such packet of the batch (k from 0) to ring
+ * (rr_start + k) & (rings - 1).  Each ring receives its packets in arrival order.  Uses no rule
+ * or neighbour table and writes nothing to the frames.
+ *   d_ring[i]      packet i's ring, | UPE_RX_FALLBACK when the cursor chose it
+ *   d_flow_hash[i] optional: flow_hash of a parsed packet, 0 otherwise
+ *   d_index        the stable partition by ring: ring r's packets, ascending, are
+ *                  d_index[start_r .. start_r + d_counts[r]), start_r = d_counts[0] + ... +
+ *                  d_counts[r - 1]
+ *   d_desc_out     optional: d_desc_out[k] = d_desc[d_index[k]]
+ *   d_counts       rings + 1 entries: packets per ring, then the number of fallback packets
+ * d_desc_out + start_r is a ready descriptor array of d_counts[r] packets over the same
+ * d_frames: worker r is then a context of its own (its own L1 caches, counters and rule_stats,
+ * as one reference worker_t, src/main.c:444-456) calling upe_gpu_process* on that segment.  Rings
+ * hold disjoint packets, so the workers' in-place rewrites do not collide.
+ * The cursor for the next batch is (rr_start + d_counts[rings]) & (rings - 1); the caller carries
+ * it, as the reference's `static rr` does (rr_start is taken & (rings - 1)).
+ * Asynchronous on `stream` like upe_gpu_process (three launches; scratch lives in the context,
+ * so a context's dispatches are queued one after another).  n == 0 zeroes d_counts and launches
+ * nothing.  -1 before any launch: rings 0, not a power of two or above UPE_RX_RINGS_MAX; a NULL
+ * required buffer with n > 0 (d_counts always); n beyond the kernels' 32-bit indexes.
+ * Out of scope, host ring mechanics: the drop of packets a full ring refuses
+ * (src/rx_pcap.c:31-36) and the 32-packet staging bursts (src/rx_pcap.c:80-92).
+ * UPE_RX_BLOCK: packets per workgroup of the dispatch kernels (batch sizes around it are where
+ * tests look). */
+#define UPE_RX_RINGS_MAX 64
+#define UPE_RX_FALLBACK 0x80000000u
+#define UPE_RX_BLOCK 1024
+int upe_gpu_rx_dispatch(upe_gpu_ctx_t *ctx, const uint8_t *d_frames, const uint64_t *d_desc,
+                        size_t n, uint32_t rings, uint32_t rr_start,
+                        uint32_t *d_ring,      /* n */
+                        uint32_t *d_flow_hash, /* n, optional */
+                        uint32_t *d_index,     /* n */
+                        uint64_t *d_desc_out,  /* n, optional */
+                        uint64_t *d_counts,    /* rings + 1 */
+                        void *stream);
 
 /* Egress list: d_index[0..*d_count) = the indexes i < n whose verdict code is `code` (e.g.
  * UPE_V_FWD), in packet order — the order process_packet queues frames for tx_send_batch

@@ -77,6 +77,7 @@
 #include <vector>
 
 #include "../../include/upe_gpu.h"
+#include "upe_rx.h"
 
 namespace {
 
@@ -2610,6 +2611,8 @@ struct upe_gpu_ctx {
     bool tss = false;
     uint32_t* compact_counts = nullptr;   // upe_gpu_compact: per-block counts
     size_t compact_alloc = 0;
+    uint32_t* rx_scratch = nullptr;       // upe_gpu_rx_dispatch: the passes' tile table (upe_rx.hip)
+    size_t rx_alloc = 0;                  // bytes
     // upe_gpu_process_segmented scratch: marks / index [ctrl_alloc], gathered windows
     uint32_t* ctrl_marks = nullptr;
     uint32_t* ctrl_index = nullptr;
@@ -3179,7 +3182,7 @@ void upe_gpu_close(upe_gpu_ctx_t* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void* bufs[] = {c->rv4, c->rv6, c->rinfo, c->stats_idx, c->gb, c->arp, c->ndp, c->st, c->stats,
                     c->pay, c->lb, c->tg4, c->tg6, c->tt4, c->tt6, c->tfs, c->fam, c->tree,
-                    c->compact_counts,
+                    c->compact_counts, c->rx_scratch,
                     c->ctrl_marks, c->ctrl_index, c->ctrl_count, c->ctrl_win, c->ctrl_lens,
                     c->hist_part};
     for (void* b : bufs)
@@ -5283,6 +5286,69 @@ int upe_gpu_compact(upe_gpu_ctx_t* c, const uint32_t* d_verdict, size_t n, uint3
                        reinterpret_cast<unsigned long long*>(d_count));
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// The RX thread's dispatch (reference src/rx_pcap.c:19-25,67-80); the kernels are upe_rx.hip's.
+// ev: NULL, or four events around the three passes.
+static int rx_dispatch(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc, size_t n,
+                       uint32_t rings, uint32_t rr_start, uint32_t* d_ring, uint32_t* d_flow_hash,
+                       uint32_t* d_index, uint64_t* d_desc_out, uint64_t* d_counts, void* stream,
+                       hipEvent_t* ev) {
+    if (!c) return fail("null context");
+    if (rings == 0 || (rings & (rings - 1)) != 0 || rings > UPE_RX_RINGS_MAX)
+        return fail("rings must be a power of two between 1 and " +
+                    std::to_string(UPE_RX_RINGS_MAX));
+    if (!d_counts || (n && (!d_frames || !d_desc || !d_ring || !d_index)))
+        return fail("null buffer");
+    if (n > 0xFFFFFFFFull - UPE_RX_BLOCK) return fail("n must fit in 32 bits");
+    DEV_SCOPE(c->device);
+    hipStream_t s = pick(c, stream);
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_counts, 0, (rings + 1) * sizeof(uint64_t), s));
+        return 0;
+    }
+    const size_t need = upe_rx_scratch_bytes((uint32_t)n, rings);
+    if (need > c->rx_alloc) {
+        if (c->rx_scratch) HIP_TRY(hipFree(c->rx_scratch));
+        c->rx_scratch = nullptr;
+        c->rx_alloc = 0;
+        HIP_TRY(hipMalloc(&c->rx_scratch, need + need / 4));
+        c->rx_alloc = need + need / 4;
+    }
+    HIP_TRY(upe_rx_launch(d_frames, d_desc, (uint32_t)n, rings, rr_start & (rings - 1), d_ring,
+                          d_flow_hash, d_index, d_desc_out, d_counts, c->rx_scratch, s, ev));
+    return 0;
+}
+
+int upe_gpu_rx_dispatch(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc, size_t n,
+                        uint32_t rings, uint32_t rr_start, uint32_t* d_ring, uint32_t* d_flow_hash,
+                        uint32_t* d_index, uint64_t* d_desc_out, uint64_t* d_counts, void* stream) {
+    return rx_dispatch(c, d_frames, d_desc, n, rings, rr_start, d_ring, d_flow_hash, d_index,
+                       d_desc_out, d_counts, stream, nullptr);
+}
+
+// Diagnostic (tools/rx_dispatch_time.py; not in the header): one dispatch of n > 0 packets with
+// HIP events around each pass; ms[0..2] = the hash, scan and scatter pass.  Synchronous.
+int upe_gpu_rx_dispatch_timed(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc,
+                              size_t n, uint32_t rings, uint32_t rr_start, uint32_t* d_ring,
+                              uint32_t* d_flow_hash, uint32_t* d_index, uint64_t* d_desc_out,
+                              uint64_t* d_counts, void* stream, float* ms) {
+    if (!c || !ms || n == 0) return fail("null context, no output or an empty batch");
+    DEV_SCOPE(c->device);
+    hipEvent_t ev[4] = {};
+    int rc = 0;
+    for (auto& e : ev)
+        if (hipEventCreate(&e) != hipSuccess) rc = fail("hipEventCreate");
+    if (rc == 0)
+        rc = rx_dispatch(c, d_frames, d_desc, n, rings, rr_start, d_ring, d_flow_hash, d_index,
+                         d_desc_out, d_counts, stream, ev);
+    if (rc == 0 && hipEventSynchronize(ev[3]) != hipSuccess) rc = fail("hipEventSynchronize");
+    for (int k = 0; k < 3 && rc == 0; ++k)
+        if (hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]) != hipSuccess)
+            rc = fail("hipEventElapsedTime");
+    for (auto& e : ev)
+        if (e) (void)hipEventDestroy(e);
+    return rc;
 }
 
 }  // extern "C"

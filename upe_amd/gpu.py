@@ -33,6 +33,11 @@ VAR_GLB = 128   # the same scanned whole (a family's list is a single catch-all)
 VAR_TREE = 192  # the same matched through the decision tree over the family lists
 VAR_SCAN = 192  # the bits of the three above
 
+# upe_gpu_rx_dispatch (include/upe_gpu.h)
+RX_RINGS_MAX = 64         # UPE_RX_RINGS_MAX
+RX_FALLBACK = 0x80000000  # UPE_RX_FALLBACK: the round-robin cursor chose the packet's ring
+RX_BLOCK = 1024           # UPE_RX_BLOCK: packets per workgroup of the dispatch kernels
+
 
 # upe_tx_batch_fn: int (*)(void *user, const uint8_t *const *frames, const size_t *lens, int count)
 TX_BATCH_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p,
@@ -120,6 +125,8 @@ def _load() -> ctypes.CDLL:
         "upe_gpu_process_batches": (I, [P, P, P, P, SZ, SZ, P]),
         "upe_gpu_process_rss": (I, [P, P, P, P, P, SZ, P]),
         "upe_gpu_compact": (I, [P, P, SZ, ctypes.c_uint32, P, P, P]),
+        "upe_gpu_rx_dispatch": (I, [P, P, P, SZ, ctypes.c_uint32, ctypes.c_uint32, P, P, P, P, P,
+                                    P]),
         "upe_gpu_process_segmented": (I, [P, P, P, P, SZ, P, SZ, P, SZ, ctypes.c_int64, P, P]),
         "upe_gpu_process_emit": (I, [P, P, P, P, P, SZ, P]),
         "upe_gpu_process_emit_tx": (I, [P, P, P, P, P, P, P, SZ, P]),
@@ -181,7 +188,7 @@ EXPORTED = ("upe_gpu_last_error", "upe_gpu_device_count", "upe_gpu_local_cpus", 
             "upe_gpu_host_unregister", "upe_gpu_process_mapped", "upe_gpu_process_mapped_emit",
             "upe_tx_flush", "upe_tx_flush_groups", "upe_gpu_process_emit_tx", "upe_gpu_hdr_layout",
             "upe_rules_compile", "upe_gpu_reload_image", "upe_rules_image_free",
-            "upe_gpu_worker_run")
+            "upe_gpu_worker_run", "upe_gpu_rx_dispatch")
 
 
 def _check(rc: int, what: str) -> None:
@@ -426,6 +433,18 @@ class GpuWorker:
         """Indexes of the packets with verdict code `code`, in packet order (device buffers)."""
         _check(LIB.upe_gpu_compact(self._ctx, _dev_ptr(verdict), n, code, _dev_ptr(index),
                                    _dev_ptr(count), stream or None), "upe_gpu_compact")
+
+    def rx_dispatch(self, frames, desc, n: int, rings: int, rr_start: int, ring, index, counts,
+                    flow_hash=None, desc_out=None, stream=None) -> None:
+        """upe_gpu_rx_dispatch: the RX thread's ring choice for a device batch (rx.dispatch_host
+        is the same on the host).  Device buffers: ring / index (n uint32), counts (rings + 1
+        uint64: packets per ring, then the fallback packets), optional flow_hash (n uint32) and
+        desc_out (n uint64, the descriptors in ring order)."""
+        _check(LIB.upe_gpu_rx_dispatch(self._ctx, _dev_ptr(frames) or None, _dev_ptr(desc) or None,
+                                       n, rings, rr_start, _dev_ptr(ring) or None,
+                                       _dev_ptr(flow_hash) or None, _dev_ptr(index) or None,
+                                       _dev_ptr(desc_out) or None, _dev_ptr(counts) or None,
+                                       stream or None), "upe_gpu_rx_dispatch")
 
     def sync(self, stream=None) -> None:
         _check(LIB.upe_gpu_sync(self._ctx, stream or None), "upe_gpu_sync")
