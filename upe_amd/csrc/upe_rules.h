@@ -1,0 +1,67 @@
+// upe_rules.h — the rule compiler (upe_rules.cpp, plain C++: no GPU, any thread): what
+// upe_gpu.hip installs into a context (struct upe_rule_image, build_image) and the cuckoo
+// placement upe_gpu_load_neigh shares with it.  The extern "C" entry points of the compiler
+// (upe_rules_compile, upe_rules_image_free, upe_rules_match_host) are in include/upe_gpu.h.
+#ifndef UPE_RULES_H
+#define UPE_RULES_H
+
+#include <vector>
+
+#include "../../include/upe_gpu.h"
+#include "upe_dev.h"
+
+namespace upe {
+
+// Tuple-space index of one family of the compiled rules (see TssGroup).
+struct TssFamily {
+    std::vector<TssGroup> groups;
+    std::vector<uint4> slots;
+    std::vector<uint16_t> fp;   // one per slot
+};
+
+// Decision-tree index over the family lists (kTreeDims comment).
+struct TreeImage {
+    std::vector<uint2> nodes;
+    std::vector<uint32_t> leaves;
+    uint32_t trees[2] = {0, 0};      // trees per family
+    uint32_t depth[2] = {0, 0};      // deepest leaf per family
+    uint32_t max_leaf = 0;           // longest leaf list
+    uint32_t swap6 = 0xFFu;          // IPv6 address words compared big-endian (tree_rule)
+};
+
+}  // namespace upe
+
+// The compiled table a context classifies with (round 6: built apart from any context, so that
+// a program's stats thread can build it while the workers keep forwarding, as the reference's
+// does before its SIGHUP swap, src/main.c:222-257): the rule words, the family lists, the
+// tuple-space index or the decision tree, and the flags the launches need.  Host memory only.
+struct upe_rule_image {
+    size_t count = 0, cap = 0, pad = 0;
+    std::vector<upe::RuleV4> v4;
+    std::vector<upe::RuleV6> v6;
+    std::vector<int2> info;
+    bool fwd4 = false, fwd6 = false;
+    uint32_t fam4 = 0, fam6 = 0, fam_all = 0, fam_x1idx = 0;
+    std::vector<uint4> fimg;
+    bool tss = false;
+    upe::TssFamily f4, f6;
+    std::vector<uint16_t> fps;
+    bool tree_ok = false;
+    std::vector<uint4> timg;
+    upe::TreeImage t;
+};
+
+namespace upe {
+
+// Compile a sorted table of `count` rules for a context whose rule_stats hold `cap` entries.
+// 0, or -1 (upe_gpu_last_error()).
+UPE_INTERNAL int build_image(const upe_rule_t* rules, size_t count, size_t cap, upe_rule_image& im);
+
+// Three-choice cuckoo placement of the neighbour indexes' keys (slot1 / slot2 / slot3): starts at
+// 2^bits >= 1.25 n slots, random-walk eviction, seeds tried, then doubles.  bits = 0 for no keys.
+UPE_INTERNAL int cuckoo3_place(const std::vector<uint32_t>& key, uint32_t& bits, uint32_t& seed,
+                               std::vector<int32_t>& slot);
+
+}  // namespace upe
+
+#endif  // UPE_RULES_H

@@ -24,10 +24,11 @@ LIB_PATH = os.environ.get("UPE_GPU_LIB_DIAG") or os.path.join(
     os.path.dirname(os.path.abspath(__file__)), "libupe_gpu.so")  # override: diagnostic builds only
 
 
-# launch_info variant bits (upe_gpu.hip classify_var)
+# launch_info variant bits (csrc/upe_gpu.hip variant_word)
 VAR_NOLB = 8    # the kernel without look-back
 VAR_RING = 16   # a ring launch whose batches are stamped
 VAR_HOST = 32   # a host path's launch (mapped host memory, host round trip)
+VAR_TX = 48     # both: the egress-list kernels (process_emit_tx)
 VAR_FAM = 64    # a linear-scan table past 64 rules, scanned through per-family rule lists
 VAR_GLB = 128   # the same scanned whole (a family's list is a single catch-all)
 VAR_TREE = 192  # the same matched through the decision tree over the family lists
