@@ -613,6 +613,80 @@ int upe_gpu_process_emit_tx(upe_gpu_ctx_t *ctx, uint8_t *d_frames, const uint64_
                             uint32_t *d_verdict, upe_hdr_rec_t *d_hdr, uint32_t *d_tx,
                             uint32_t *d_tx_count, size_t n, void *stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Egress batch: the forwarded frames packed back to back on the device                        */
+/* ------------------------------------------------------------------------------------------ */
+/* The bytes that go out, for a classified batch resident in GPU memory: the frames process_packet
+ * queues for tx_send_batch (reference src/worker.c:240-243), rewritten exactly as it leaves them
+ * in b->data (src/worker.c:162-244), in the order it queues them (src/worker.c:287-303), back to
+ * back in d_out.  The output is itself a "Batch layout" with its own descriptors: a TX path
+ * copies back (or DMAs) only the forwarded bytes, in one piece; a next stage classifies it as its
+ * input batch; upe_tx_flush_packed makes the reference worker's TX calls from it.
+ *
+ * Packing rule.  Let f_0 < f_1 < ... be the packets whose verdict code is UPE_V_FWD (only the code
+ * of a verdict word is read) and len_k the length in d_desc[f_k].  Packed frame k starts at
+ * o_k = the sum over j < k of (len_j + 15) & ~15, and
+ *   d_out_desc[k]  = UPE_DESC(o_k, len_k)
+ *   d_out_index[k] = f_k                              (optional)
+ *   d_out[o_k .. o_k + len_k) = the frame; the bytes up to the next 16-byte boundary are zero,
+ *                    so every byte of [0, bytes) is defined.
+ * The frame bytes are, with d_hdr == NULL, a copy of the frame (the batch went through
+ * upe_gpu_process, _rss or _segmented, which rewrote it in place); with d_hdr, the untouched
+ * frame with its record applied byte for byte as upe_hdr_apply does (the batch went through
+ * upe_gpu_process_emit, _emit_tx, _ring_emit or _queue_emit).  Packet i's record is found by the
+ * UPE_HDR_SLOT rule, slot 64 * (i / 64) + its rank among the forwarded packets of its 64-group;
+ * rec[i] is never read.  A patched byte position at or beyond len is not written.
+ *
+ * Capacity.  Frame k is packed only if o_k + ((len_k + 15) & ~15) <= out_bytes; offsets ascend,
+ * so the packed frames are a prefix, counted in `packed`; `need` is the size to retry with.
+ * Nothing at or beyond d_out + out_bytes is written, and entries of d_out_desc / d_out_index
+ * from `packed` on are not written.
+ *
+ * Not done here: the UPE_FRAME_TAIL bytes after the last frame are not written (a caller that
+ * feeds d_out to another classify sizes it for them, as for any batch).  The call needs FULL
+ * frames, as upe_gpu_process_segmented does: a batch of header windows (UPE_HDR_WINDOW) is not
+ * valid input, the bytes past a window would be packed as payload.  Frames are read in whole
+ * 16-byte quads (the quad holding a frame's last byte is read whole, never a quad past it).  ARP
+ * requests answered in place (UPE_VF_ARP_REPLY, code DROP_PARSE) are not in the output: the
+ * reference sends those at once through tx_send, outside the batch queue (src/worker.c:40-52).
+ *
+ * Asynchronous on `stream` (three launches; scratch lives in the context, so a context's packs
+ * are queued one after another).  n == 0 zeroes *d_info and launches nothing.  -1 before any
+ * launch: a NULL required pointer with n > 0 (d_info always); d_out not 16-byte aligned; n beyond
+ * the kernels' 32-bit indexes; d_out overlapping d_frames in address — the call cannot see where
+ * the frames end, so d_frames counts up to the end of the device allocation that holds it (a
+ * caller carving both out of one allocation puts d_out below d_frames).
+ * UPE_EGRESS_BLOCK: packets per workgroup of the pack kernels (batch sizes around it are where
+ * tests look). */
+#define UPE_EGRESS_BLOCK 1024
+typedef struct {
+    uint64_t frames; /* forwarded packets in the batch */
+    uint64_t packed; /* of those, written to d_out (a prefix in packet order) */
+    uint64_t bytes;  /* bytes of d_out used by the packed frames, padding included */
+    uint64_t need;   /* bytes all `frames` would use (== bytes when everything fitted) */
+} upe_egress_info_t;
+int upe_gpu_egress_pack(upe_gpu_ctx_t *ctx, const uint8_t *d_frames, const uint64_t *d_desc,
+                        const uint32_t *d_verdict,
+                        const upe_hdr_rec_t *d_hdr, /* NULL: frames were rewritten in place */
+                        size_t n,
+                        uint8_t *d_out, size_t out_bytes,
+                        uint64_t *d_out_desc,       /* n */
+                        uint32_t *d_out_index,      /* n, optional */
+                        upe_egress_info_t *d_info,  /* device, 32 bytes */
+                        void *stream);
+
+/* The reference worker's TX calls (src/worker.c:287-303) from a packed egress batch copied to the
+ * host (h_out[0 .. info.bytes), h_out_desc, h_out_index, count = info.packed): the same calls,
+ * arguments and accounting as upe_tx_flush over the classified ingress batch — one `send` per
+ * input burst (h_out_index[k] / burst) that forwarded anything, at most UPE_TX_BATCH_MAX frames
+ * per call — with the frame pointers pointing into h_out; the ingress buffer is not needed.  All
+ * arguments are checked before the first `send`: -1, with no call made, for a burst of 0 or above
+ * UPE_TX_BATCH_MAX, a NULL argument with count > 0, or an index list that does not ascend
+ * strictly. */
+int upe_tx_flush_packed(const uint8_t *h_out, const uint64_t *h_out_desc,
+                        const uint32_t *h_out_index, size_t count, size_t burst,
+                        upe_tx_batch_fn send, void *user, uint64_t *forwarded, uint64_t *dropped);
+
 /* A batch with exact control-packet semantics, as the reference's burst loop runs it
  * (src/worker.c:23-104 inside process_packet): an ARP packet with the Ethernet/IPv4 header, or
  * an NDP NS/NA carrying a link-layer address option, writes a neighbour table, and every later
@@ -738,5 +812,6 @@ UPE_STATIC_ASSERT(offsetof(upe_ndp_entry_t, valid) == 32, "ndp_entry_t.valid");
 UPE_STATIC_ASSERT(sizeof(upe_rule_stat_t) == 16, "rule_stat_t layout");
 UPE_STATIC_ASSERT(sizeof(upe_hdr_rec_t) == 16, "upe_hdr_rec_t layout");
 UPE_STATIC_ASSERT(sizeof(upe_launch_info_t) == 24, "upe_launch_info_t layout");
+UPE_STATIC_ASSERT(sizeof(upe_egress_info_t) == 32, "upe_egress_info_t layout");
 
 #endif /* UPE_GPU_H */

@@ -78,6 +78,7 @@
 #include "../../include/upe_gpu.h"
 #include "upe_dev.h"
 #include "upe_rules.h"
+#include "upe_egress.h"
 #include "upe_rx.h"
 
 using namespace upe;
@@ -2501,6 +2502,8 @@ struct upe_gpu_ctx {
     size_t compact_alloc = 0;
     uint32_t* rx_scratch = nullptr;       // upe_gpu_rx_dispatch: the passes' tile table (upe_rx.hip)
     size_t rx_alloc = 0;                  // bytes
+    void* eg_scratch = nullptr;           // upe_gpu_egress_pack: the tile table (upe_egress.hip)
+    size_t eg_alloc = 0;                  // bytes
     // upe_gpu_process_segmented scratch: marks / index [ctrl_alloc], gathered windows
     uint32_t* ctrl_marks = nullptr;
     uint32_t* ctrl_index = nullptr;
@@ -2970,7 +2973,7 @@ void upe_gpu_close(upe_gpu_ctx_t* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void* bufs[] = {c->rv4, c->rv6, c->rinfo, c->stats_idx, c->gb, c->arp, c->ndp, c->st, c->stats,
                     c->pay, c->lb, c->tg4, c->tg6, c->tt4, c->tt6, c->tfs, c->fam, c->tree,
-                    c->compact_counts, c->rx_scratch,
+                    c->compact_counts, c->rx_scratch, c->eg_scratch,
                     c->ctrl_marks, c->ctrl_index, c->ctrl_count, c->ctrl_win, c->ctrl_lens,
                     c->hist_part};
     for (void* b : bufs)
@@ -4160,6 +4163,102 @@ int upe_gpu_rx_dispatch_timed(upe_gpu_ctx_t* c, const uint8_t* d_frames, const u
     for (int k = 0; k < 3 && rc == 0; ++k)
         if (hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]) != hipSuccess)
             rc = fail("hipEventElapsedTime");
+    for (auto& e : ev)
+        if (e) (void)hipEventDestroy(e);
+    return rc;
+}
+
+// The egress batch builder (reference src/worker.c:240-243, 287-303: the frames queued for
+// tx_send_batch, in order); the kernels are upe_egress.hip's.  ev: NULL, or four events around
+// the three passes.
+static int egress_pack(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc,
+                       const uint32_t* d_verdict, const upe_hdr_rec_t* d_hdr, size_t n,
+                       uint8_t* d_out, size_t out_bytes, uint64_t* d_out_desc,
+                       uint32_t* d_out_index, upe_egress_info_t* d_info, void* stream,
+                       hipEvent_t* ev) {
+    if (!c) return fail("null context");
+    if (!d_info || (n && (!d_frames || !d_desc || !d_verdict || !d_out || !d_out_desc)))
+        return fail("null buffer");
+    if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0 ||
+        (reinterpret_cast<uintptr_t>(d_frames) & 15u) != 0 ||
+        (reinterpret_cast<uintptr_t>(d_hdr) & 15u) != 0)
+        return fail("d_out, d_frames and d_hdr must be 16-byte aligned");
+    if (n > 0xFFFFFFFFull - UPE_EGRESS_BLOCK) return fail("n must fit in 32 bits");
+    DEV_SCOPE(c->device);
+    hipStream_t s = pick(c, stream);
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_info, 0, sizeof(upe_egress_info_t), s));
+        return 0;
+    }
+    // where the frames end is not known here: they count up to the end of their allocation
+    const uintptr_t fr = reinterpret_cast<uintptr_t>(d_frames);
+    const uintptr_t out = reinterpret_cast<uintptr_t>(d_out);
+    uintptr_t fr_end = fr + 1;
+    hipDeviceptr_t abase = nullptr;
+    size_t asize = 0;
+    if (hipMemGetAddressRange(&abase, &asize, const_cast<uint8_t*>(d_frames)) == hipSuccess)
+        fr_end = reinterpret_cast<uintptr_t>(abase) + asize;
+    else
+        (void)hipGetLastError();   // not a device allocation's pointer (mapped host memory)
+    if (out < fr_end && fr < out + (out_bytes ? out_bytes : 1))
+        return fail("d_out overlaps d_frames");
+    const size_t need = upe_egress_scratch_bytes((uint32_t)n);
+    if (need > c->eg_alloc) {
+        if (c->eg_scratch) HIP_TRY(hipFree(c->eg_scratch));
+        c->eg_scratch = nullptr;
+        c->eg_alloc = 0;
+        HIP_TRY(hipMalloc(&c->eg_scratch, need + need / 4));
+        c->eg_alloc = need + need / 4;
+    }
+    HIP_TRY(upe_egress_launch(d_frames, d_desc, d_verdict, d_hdr, (uint32_t)n, d_out, out_bytes,
+                              d_out_desc, d_out_index, d_info, c->eg_scratch, s, ev));
+    return 0;
+}
+
+int upe_gpu_egress_pack(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc,
+                        const uint32_t* d_verdict, const upe_hdr_rec_t* d_hdr, size_t n,
+                        uint8_t* d_out, size_t out_bytes, uint64_t* d_out_desc,
+                        uint32_t* d_out_index, upe_egress_info_t* d_info, void* stream) {
+    return egress_pack(c, d_frames, d_desc, d_verdict, d_hdr, n, d_out, out_bytes, d_out_desc,
+                       d_out_index, d_info, stream, nullptr);
+}
+
+// Diagnostic (tools/egress_pack_time.py; not in the header): one pack of n > 0 packets with HIP
+// events around each pass, then a plain device-to-device copy of the packed bytes (info.bytes,
+// d_out -> d_copy, out_bytes of room) on the same stream: the floor of the copy pass.
+// ms[0..3] = the size, scan and copy pass and that copy.  Synchronous.
+int upe_gpu_egress_pack_timed(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc,
+                              const uint32_t* d_verdict, const upe_hdr_rec_t* d_hdr, size_t n,
+                              uint8_t* d_out, size_t out_bytes, uint64_t* d_out_desc,
+                              uint32_t* d_out_index, upe_egress_info_t* d_info, uint8_t* d_copy,
+                              void* stream, float* ms) {
+    if (!c || !ms || !d_copy || n == 0)
+        return fail("null context, no output or an empty batch");
+    DEV_SCOPE(c->device);
+    hipStream_t s = pick(c, stream);
+    hipEvent_t ev[6] = {};
+    int rc = 0;
+    for (auto& e : ev)
+        if (hipEventCreate(&e) != hipSuccess) rc = fail("hipEventCreate");
+    if (rc == 0)
+        rc = egress_pack(c, d_frames, d_desc, d_verdict, d_hdr, n, d_out, out_bytes, d_out_desc,
+                         d_out_index, d_info, stream, ev);
+    upe_egress_info_t info = {};
+    if (rc == 0 && (hipMemcpyAsync(&info, d_info, sizeof(info), hipMemcpyDeviceToHost, s) !=
+                        hipSuccess ||
+                    hipStreamSynchronize(s) != hipSuccess))
+        rc = fail("reading the pack's info");
+    if (rc == 0 && (hipEventRecord(ev[4], s) != hipSuccess ||
+                    hipMemcpyAsync(d_copy, d_out, info.bytes, hipMemcpyDeviceToDevice, s) !=
+                        hipSuccess ||
+                    hipEventRecord(ev[5], s) != hipSuccess ||
+                    hipEventSynchronize(ev[5]) != hipSuccess))
+        rc = fail("the device-to-device copy");
+    for (int k = 0; k < 3 && rc == 0; ++k)
+        if (hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]) != hipSuccess)
+            rc = fail("hipEventElapsedTime");
+    if (rc == 0 && hipEventElapsedTime(&ms[3], ev[4], ev[5]) != hipSuccess)
+        rc = fail("hipEventElapsedTime");
     for (auto& e : ev)
         if (e) (void)hipEventDestroy(e);
     return rc;

@@ -401,4 +401,37 @@ int upe_tx_flush_groups(const uint8_t *h_frames, const uint64_t *h_desc, const u
     return 0;
 }
 
+/* The same calls from the packed egress batch of upe_gpu_egress_pack: frame k lies at
+ * h_out + (h_out_desc[k] >> 16) and belongs to input burst h_out_index[k] / burst.  Everything is
+ * checked before the first send (all or nothing). */
+int upe_tx_flush_packed(const uint8_t *h_out, const uint64_t *h_out_desc,
+                        const uint32_t *h_out_index, size_t count, size_t burst,
+                        upe_tx_batch_fn send, void *user, uint64_t *forwarded, uint64_t *dropped) {
+    if (burst == 0 || burst > UPE_TX_BATCH_MAX)
+        return host_fail("upe_tx_flush_packed: burst %d must be 1..UPE_TX_BATCH_MAX", (int)burst, "");
+    if (count && (!h_out || !h_out_desc || !h_out_index || !send))
+        return host_fail("upe_tx_flush_packed: null argument%.0d%s", 0, "");
+    for (size_t k = 1; k < count; k++)
+        if (h_out_index[k] <= h_out_index[k - 1])
+            return host_fail("upe_tx_flush_packed: index list entry %d does not ascend%s", (int)k, "");
+    const uint8_t *frames[UPE_TX_BATCH_MAX];
+    size_t lens[UPE_TX_BATCH_MAX];
+    size_t k = 0;
+    while (k < count) {
+        /* strictly ascending indexes: a burst holds at most `burst` <= UPE_TX_BATCH_MAX of them */
+        const size_t b = h_out_index[k] / burst;
+        int c = 0;
+        for (; k < count && h_out_index[k] / burst == b; k++) {
+            frames[c] = h_out + (h_out_desc[k] >> 16);
+            lens[c++] = (size_t)(h_out_desc[k] & 0xFFFFu);
+        }
+        int sent = send(user, frames, lens, c);
+        if (sent < 0) sent = 0;
+        if (sent > c) sent = c;
+        if (forwarded) *forwarded += (uint64_t)sent;
+        if (dropped) *dropped += (uint64_t)(c - sent);
+    }
+    return 0;
+}
+
 int upe_gpu_hdr_layout(void) { return UPE_HDR_LAYOUT; }

@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from .layout import (ARP_DTYPE, BATCH_INFO_DTYPE, COUNTERS_DTYPE, FLOW_KEY_DTYPE, L1_DTYPE,
-                     LAUNCH_INFO_DTYPE, NDP_DTYPE, RULE_DTYPE, RULE_INDEX_INFO_DTYPE,
+                     EGRESS_INFO_DTYPE, LAUNCH_INFO_DTYPE, NDP_DTYPE, RULE_DTYPE, RULE_INDEX_INFO_DTYPE,
                      RULE_STAT_DTYPE)
 
 LIB_PATH = os.environ.get("UPE_GPU_LIB_DIAG") or os.path.join(
@@ -38,6 +38,9 @@ VAR_SCAN = 192  # the bits of the three above
 RX_RINGS_MAX = 64         # UPE_RX_RINGS_MAX
 RX_FALLBACK = 0x80000000  # UPE_RX_FALLBACK: the round-robin cursor chose the packet's ring
 RX_BLOCK = 1024           # UPE_RX_BLOCK: packets per workgroup of the dispatch kernels
+
+# upe_gpu_egress_pack (include/upe_gpu.h)
+EGRESS_BLOCK = 1024       # UPE_EGRESS_BLOCK: packets per workgroup of the pack kernels
 
 
 # upe_tx_batch_fn: int (*)(void *user, const uint8_t *const *frames, const size_t *lens, int count)
@@ -128,6 +131,8 @@ def _load() -> ctypes.CDLL:
         "upe_gpu_compact": (I, [P, P, SZ, ctypes.c_uint32, P, P, P]),
         "upe_gpu_rx_dispatch": (I, [P, P, P, SZ, ctypes.c_uint32, ctypes.c_uint32, P, P, P, P, P,
                                     P]),
+        "upe_gpu_egress_pack": (I, [P, P, P, P, P, SZ, P, SZ, P, P, P, P]),
+        "upe_tx_flush_packed": (I, [P, P, P, SZ, SZ, TX_BATCH_FN, P, P, P]),
         "upe_gpu_process_segmented": (I, [P, P, P, P, SZ, P, SZ, P, SZ, ctypes.c_int64, P, P]),
         "upe_gpu_process_emit": (I, [P, P, P, P, P, SZ, P]),
         "upe_gpu_process_emit_tx": (I, [P, P, P, P, P, P, P, SZ, P]),
@@ -189,7 +194,8 @@ EXPORTED = ("upe_gpu_last_error", "upe_gpu_device_count", "upe_gpu_local_cpus", 
             "upe_gpu_host_unregister", "upe_gpu_process_mapped", "upe_gpu_process_mapped_emit",
             "upe_tx_flush", "upe_tx_flush_groups", "upe_gpu_process_emit_tx", "upe_gpu_hdr_layout",
             "upe_rules_compile", "upe_gpu_reload_image", "upe_rules_image_free",
-            "upe_gpu_worker_run", "upe_gpu_rx_dispatch")
+            "upe_gpu_worker_run", "upe_gpu_rx_dispatch", "upe_gpu_egress_pack",
+            "upe_tx_flush_packed")
 
 
 def _check(rc: int, what: str) -> None:
@@ -447,6 +453,28 @@ class GpuWorker:
                                        _dev_ptr(desc_out) or None, _dev_ptr(counts) or None,
                                        stream or None), "upe_gpu_rx_dispatch")
 
+    def egress_pack(self, frames, desc, verdict, n: int, out, out_bytes: int, out_desc, info,
+                    hdr=None, out_index=None, stream=None) -> None:
+        """upe_gpu_egress_pack: the forwarded frames of a classified device batch packed back to
+        back into `out` (egress.pack_host is the same on the host).  Device buffers: out
+        (out_bytes, 16-byte aligned), out_desc (n uint64), info (32 bytes, EGRESS_INFO_DTYPE),
+        optional out_index (n uint32); hdr = the emit-mode records of the launch that classified
+        the batch, or None when the frames were rewritten in place."""
+        _check(LIB.upe_gpu_egress_pack(self._ctx, _dev_ptr(frames) or None, _dev_ptr(desc) or None,
+                                       _dev_ptr(verdict) or None, _dev_ptr(hdr) or None, n,
+                                       _dev_ptr(out) or None, out_bytes,
+                                       _dev_ptr(out_desc) or None, _dev_ptr(out_index) or None,
+                                       _dev_ptr(info) or None, stream or None),
+               "upe_gpu_egress_pack")
+
+    def fetch_egress_info(self, info) -> np.ndarray:
+        """The upe_egress_info_t a pack wrote to the device (synchronises)."""
+        x = np.zeros(1, EGRESS_INFO_DTYPE)
+        self.sync()
+        self.d2h(x, info)
+        self.sync()
+        return x[0]
+
     def sync(self, stream=None) -> None:
         _check(LIB.upe_gpu_sync(self._ctx, stream or None), "upe_gpu_sync")
 
@@ -634,6 +662,46 @@ def tx_flush(frames: np.ndarray, desc: np.ndarray, verdict: np.ndarray, burst: i
                               ctypes.byref(drp))
     if rc != 0:
         raise UpeGpuError(f"upe_tx_flush: {LIB.upe_host_last_error().decode()}")
+    return batches, int(fwd.value), int(drp.value)
+
+
+def tx_flush_packed(out: np.ndarray, out_desc: np.ndarray, out_index: np.ndarray,
+                    burst: int = 32, sent_of=None):
+    """upe_tx_flush_packed over a packed egress batch on the host (the outputs of
+    upe_gpu_egress_pack / egress.pack_host, cut to info.packed entries): returns (batches,
+    forwarded, dropped) in tx_flush's shape — one (packet indexes of the ingress batch, frame
+    bytes) pair per TX call in call order — so the two compare directly."""
+    out = np.ascontiguousarray(out, dtype=np.uint8)
+    out_desc = np.ascontiguousarray(out_desc, dtype=np.uint64)
+    out_index = np.ascontiguousarray(out_index, dtype=np.uint32)
+    assert out_desc.shape[0] == out_index.shape[0]
+    base = out.ctypes.data
+    offs = (out_desc >> np.uint64(16)).tolist()
+    batches = []
+    seen, bad = [0], []   # entries handed over so far: the calls walk the list in order
+
+    def cb(user, fr, lens, count):
+        idx, data = [], []
+        for k in range(count):
+            off = fr[k] - base
+            if off != offs[seen[0]]:   # an exception cannot cross the C caller: raised below
+                bad.append(f"frame pointer {off} is not entry {seen[0]}'s")
+            idx.append(int(out_index[seen[0]]))
+            data.append(bytes(out[off:off + lens[k]]))
+            seen[0] += 1
+        batches.append((np.array(idx, np.int64), data))
+        return count if sent_of is None else int(sent_of(count))
+
+    fn = TX_BATCH_FN(cb)
+    fwd = ctypes.c_uint64(0)
+    drp = ctypes.c_uint64(0)
+    rc = LIB.upe_tx_flush_packed(_np_ptr(out), _np_ptr(out_desc), _np_ptr(out_index),
+                                 int(out_desc.shape[0]), int(burst), fn, None, ctypes.byref(fwd),
+                                 ctypes.byref(drp))
+    if rc != 0:
+        raise UpeGpuError(f"upe_tx_flush_packed: {LIB.upe_host_last_error().decode()}")
+    if bad:
+        raise UpeGpuError(f"upe_tx_flush_packed: {bad[0]}")
     return batches, int(fwd.value), int(drp.value)
 
 

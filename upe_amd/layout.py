@@ -59,6 +59,10 @@ LAUNCH_INFO_DTYPE = np.dtype({"names": ["variant", "grid", "deferred", "launches
                               "formats": ["<u4", "<u4", "<u4", "<u8"],
                               "offsets": [0, 4, 8, 16], "itemsize": 24})
 
+# upe_egress_info_t (include/upe_gpu.h)
+EGRESS_INFO_DTYPE = np.dtype([("frames", "<u8"), ("packed", "<u8"), ("bytes", "<u8"),
+                              ("need", "<u8")])
+
 # flow_key_t (reference include/parser.h:134-141; upe_flow_key_t, 44 bytes)
 FLOW_KEY_DTYPE = np.dtype({"names": ["ip_ver", "src_ip", "dst_ip", "src_port", "dst_port",
                                      "protocol"],
