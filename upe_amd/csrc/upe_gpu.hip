@@ -77,6 +77,7 @@
 
 #include "../../include/upe_gpu.h"
 #include "upe_dev.h"
+#include "upe_plan.h"
 #include "upe_rules.h"
 #include "upe_egress.h"
 #include "upe_rx.h"
@@ -85,21 +86,10 @@ using namespace upe;
 
 namespace {
 
-#ifndef UPE_BLOCK
-#define UPE_BLOCK 1024
-#endif
-constexpr int kBlock = UPE_BLOCK;      // threads per workgroup = packets per tile
-constexpr int kWaves = kBlock / 64;    // 64-packet chunks per tile
-constexpr int kTile = kBlock;
-
 #ifndef UPE_WAVES_PER_SIMD
 #define UPE_WAVES_PER_SIMD 4
 #endif
 constexpr int kWavesPerSimd = UPE_WAVES_PER_SIMD;   // 4 -> VGPR budget 128, 8 -> 64
-#ifndef UPE_LDS_STATS_MAX
-#define UPE_LDS_STATS_MAX 4096
-#endif
-constexpr int kLdsStatsMax = UPE_LDS_STATS_MAX;   // rule_stats in the classify kernel's LDS up to here
 constexpr int kStatReps = 8;   // replicas of the per-sorted-index rule_stats (summed on the host)
 // Claim the next chunk after finishing the current one once this few chunks are unclaimed.
 #ifndef UPE_LATE_CLAIM
@@ -114,30 +104,13 @@ constexpr uint32_t kLateClaim = UPE_LATE_CLAIM;
 #ifndef UPE_MID_PREFETCH
 #define UPE_MID_PREFETCH 1
 #endif
-// Neighbour indexes staged in LDS (one workgroup per CU, so a CU reads them once per launch):
-// ARP up to 2048 slots (32 KB), NDP up to 2048 slots (64 KB), within kLdsDynMax of dynamic LDS.
-#ifndef UPE_ARP_LDS_SLOTS
-#define UPE_ARP_LDS_SLOTS 2048
-#endif
-#ifndef UPE_NDP_LDS_SLOTS
-#define UPE_NDP_LDS_SLOTS 2048
-#endif
-constexpr uint32_t kArpLdsSlots = UPE_ARP_LDS_SLOTS;
-constexpr uint32_t kNdpLdsSlots = UPE_NDP_LDS_SLOTS;
-constexpr size_t kLdsDynMax = 152 * 1024;   // 160 KB per CU less the static LDS (7 KB at most)
 constexpr int kReps = 32;              // replicas of the per-batch accumulators
-constexpr int kRingMax = 64;           // batches of a ring launch whose completion is stamped
 // Cache policy of the emit-mode record store: sc1 (buffer aux 16) writes the records through
 // and drops their lines from the XCD's L2, so the end of a launch has ~16 MB less dirty data to
 // write back at the kernel boundary (config B 24.5 -> 24.1 us per 1M batch; nt 24.5, sc0 sc1
 // 24.2).  The verdict words are written through too (B 24.25 -> 24.1 us); the in-place 16-byte
 // header stores are not (written through they were slower: 33.7 -> 35.4 us, partial lines).
 constexpr int kRecAux = 16;
-
-#ifndef UPE_FAM_LDS
-#define UPE_FAM_LDS 1
-#endif
-constexpr bool kFamLds = UPE_FAM_LDS;
 
 // L1 state in word form + whether each entry agrees with the current neighbour snapshot.
 // DevState keeps two, by batch parity (see "Sequential state between batches").
@@ -293,37 +266,8 @@ struct Args {
     unsigned long long* ring_t0;
 };
 
-// ---- classify kernel variants ----------------------------------------------------------------
-// What a launch is for.  Host runs the same code as Device: it is a name, so that a profile of a
-// process that also classifies device-resident batches keeps the host paths' launches
-// (upe_gpu_process_mapped / upe_gpu_process_host) apart.  Ring: a ring launch that stamps its
-// batches' completion (upe_gpu_process_ring_emit).  Tx: the egress-list kernels
-// (upe_gpu_process_emit_tx).
-enum class Path { Device, Ring, Host, Tx };
-// One upe_classify instantiation.  nolb: no look-back (lean only).  scan: how a linear-scan table
-// is matched (never with tuple space): 0 small table (LDS copy), 1 its family lists (FamTable),
-// 2 the whole table through the scalar unit, 3 the decision tree over the family lists.
-struct Variant {
-    bool tss, emit, lean, nolb;
-    Path path;
-    int scan;
-};
-// The instantiated variants: every combination a launch can ask for.
-constexpr bool variant_built(Variant v) {
-    if (v.nolb && !v.lean) return false;
-    if (v.scan && v.tss) return false;
-    if (v.path == Path::Tx) return v.emit;
-    if (v.path == Path::Ring) return v.emit && v.lean && !v.tss;
-    return true;
-}
-// upe_launch_info_t.variant (include/upe_gpu.h): bit 0 emit, 1 tuple space, 2 lean, 3 no
-// look-back, 4 ring, 5 host path (4 and 5 together: the egress-list kernels), 6-7 scan.
-constexpr uint32_t variant_word(Variant v) {
-    const bool ring = v.path == Path::Ring || v.path == Path::Tx;
-    const bool host = v.path == Path::Host || v.path == Path::Tx;
-    return (v.emit ? 1u : 0u) | (v.tss ? 2u : 0u) | (v.lean ? 4u : 0u) | (v.nolb ? 8u : 0u) |
-           (ring ? 16u : 0u) | (host ? 32u : 0u) | (uint32_t)v.scan << 6;
-}
+// (the classify kernel variants, Path / Variant / variant_word: upe_plan.h)
+
 // Batch k's state slots, from Args (DevState comment).
 __device__ __forceinline__ const DevL1* l1_in(const Args& a) { return &a.st->l1[a.k6 % 2].s; }
 __device__ __forceinline__ DevL1* l1_out(const Args& a) { return &a.st->l1[(a.k6 + 1) % 2].s; }
@@ -2155,16 +2099,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerSimd) upe_classify(Args a) {
 // packets a round spent ~300 us per 16M batch waiting on them; eight a round 69.5 us, sixteen
 // 62.6 us, thirty-two slower again).
 // ------------------------------------------------------------------------------------------
-#ifndef UPE_HIST_RANGE
-#define UPE_HIST_RANGE 16384
-#endif
-constexpr uint32_t kHistRange = UPE_HIST_RANGE;   // most rules per workgroup: 128 KB of LDS
-constexpr uint32_t kHistChunk = 1u << 24;   // most packets per workgroup
-constexpr uint32_t kHistChunkMin = 8192;
-#ifndef UPE_HIST_TARGET
-#define UPE_HIST_TARGET 256
-#endif
-constexpr uint32_t kHistTarget = UPE_HIST_TARGET;   // workgroups per group-by launch
+// (kHistRange, kHistChunk, kHistChunkMin, kHistTarget: upe_plan.h)
 constexpr int kHistBlock = 1024;
 #ifndef UPE_HIST_PER
 #define UPE_HIST_PER 16
@@ -2358,6 +2293,75 @@ struct DevScope {
     DevScope dev_scope_(dev);                                                                \
     HIP_TRY(dev_scope_.e)
 
+// A device allocation of `cap` elements that its holder owns: freed with it, movable, not
+// copyable.  It converts to the raw pointer, which is what kernels, Args and DevState take.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p = o.p, cap = o.cap;
+            o.p = nullptr, o.cap = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    // Room for `count` elements: when there is not, the old allocation is freed first and one of
+    // `want` elements (>= count: each caller's growth formula) made.  Nothing is kept across a
+    // growth, and after a failed one the buffer holds nothing.
+    int reserve(size_t count, size_t want) {
+        if (count <= cap) return 0;
+        reset();
+        HIP_TRY(hipMalloc(&p, want * sizeof(T)));
+        cap = want;
+        return 0;
+    }
+    // (an empty buffer) `count` elements uploaded from the host; none: stays empty
+    int put(const T* src, size_t count) {
+        if (reserve(count, count) != 0) return -1;
+        if (count) HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
+        return 0;
+    }
+    // (an empty buffer) `count` zeroed elements
+    int zeros(size_t count) {
+        if (reserve(count, count) != 0) return -1;
+        HIP_TRY(hipMemset(p, 0, count * sizeof(T)));
+        return 0;
+    }
+    operator T*() const { return p; }
+    T* operator->() const { return p; }
+};
+
+// The timing events of one diagnostic call, destroyed with it.
+template <int N>
+struct Events {
+    hipEvent_t e[N] = {};
+    Events() = default;
+    Events(const Events&) = delete;
+    Events& operator=(const Events&) = delete;
+    ~Events() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    int create() {
+        for (hipEvent_t& x : e) HIP_TRY(hipEventCreate(&x));
+        return 0;
+    }
+    int elapsed(float* ms, int from, int to) {
+        HIP_TRY(hipEventElapsedTime(ms, e[from], e[to]));
+        return 0;
+    }
+};
+
 // ------------------------------------------------------------------------------------------
 // Control packets that write a neighbour table (upe_gpu_process_segmented).  A packet is
 // marked when handle_control_packet (reference src/worker.c:23-104) may call arp_update or
@@ -2463,11 +2467,10 @@ struct upe_gpu_ctx {
     hipStream_t stream = nullptr;
     size_t cap = 0;                // rule_stats capacity
     // rules
-    RuleV4* rv4 = nullptr;
-    RuleV6* rv6 = nullptr;
-    int2* rinfo = nullptr;
-    uint4* fam = nullptr;                      // FamTable image (linear-scan tables > kSmallRules)
-    size_t fam_alloc = 0;                      // bytes
+    DevBuf<RuleV4> rv4;
+    DevBuf<RuleV6> rv6;
+    DevBuf<int2> rinfo;
+    DevBuf<uint4> fam;                         // FamTable image (linear-scan tables > kSmallRules)
     uint32_t fam4 = 0, fam6 = 0;
     uint32_t fam_all = 0;
     // whether a packet of each family can be forwarded at all under the current table: some
@@ -2475,66 +2478,54 @@ struct upe_gpu_ctx {
     bool fwd4 = true, fwd6 = true;
     uint32_t fam_x1idx = 0;
     // decision-tree index over the family lists (null / tree_ok false when not used)
-    uint4* tree = nullptr;
+    DevBuf<uint4> tree;
     uint32_t tree_words = 0, tree_loff = 0;
     bool tree_ok = false;
     bool tree_stage = true;                    // stage the image in LDS when it fits
     upe_rule_index_info_t tree_info = {};
-    size_t rules_alloc = 0;
     uint32_t nrules = 0, nrules_pad = 0;
-    unsigned long long* stats_idx = nullptr;   // [rules_alloc][2] totals per sorted index
+    DevBuf<unsigned long long> stats_idx;      // [kStatReps][pad][2] totals per sorted index, pad
+                                               // the largest table so far
     bool host_tag = false;   // launches on behalf of a host-side loop (upe_gpu_tag_host)
-    unsigned long long* hist_part = nullptr;   // [chunks][nrules_pad] dense group-by partials
-    size_t hist_part_alloc = 0;
-    void* gb = nullptr;                        // [gb_alloc] u32: group-by keys or u16 lengths
-    size_t gb_alloc = 0;
+    DevBuf<unsigned long long> hist_part;      // [chunks][nrules] dense group-by partials
+    DevBuf<uint32_t> gb;                       // group-by keys (u32), or u16 lengths
     std::vector<int2> rinfo_host;              // (action, rule_id) per sorted index
     // tuple-space index of large tables (null when the linear scan is used)
-    TssGroup* tg4 = nullptr;
-    TssGroup* tg6 = nullptr;
-    uint4* tt4 = nullptr;
-    uint4* tt6 = nullptr;
-    uint16_t* tfs = nullptr;          // staged fingerprint image
+    DevBuf<TssGroup> tg4, tg6;
+    DevBuf<uint4> tt4, tt6;
+    DevBuf<uint16_t> tfs;             // staged fingerprint image
     uint32_t nfs = 0;                 // its length in uint4
     uint32_t ng4 = 0, ng6 = 0;
     bool tss = false;
-    uint32_t* compact_counts = nullptr;   // upe_gpu_compact: per-block counts
-    size_t compact_alloc = 0;
-    uint32_t* rx_scratch = nullptr;       // upe_gpu_rx_dispatch: the passes' tile table (upe_rx.hip)
-    size_t rx_alloc = 0;                  // bytes
-    void* eg_scratch = nullptr;           // upe_gpu_egress_pack: the tile table (upe_egress.hip)
-    size_t eg_alloc = 0;                  // bytes
-    // upe_gpu_process_segmented scratch: marks / index [ctrl_alloc], gathered windows
-    uint32_t* ctrl_marks = nullptr;
-    uint32_t* ctrl_index = nullptr;
-    uint64_t* ctrl_count = nullptr;
-    size_t ctrl_alloc = 0;
-    uint8_t* ctrl_win = nullptr;
-    uint32_t* ctrl_lens = nullptr;
-    size_t ctrl_win_alloc = 0;
+    DevBuf<uint32_t> compact_counts;      // upe_gpu_compact: per-block counts
+    DevBuf<uint8_t> rx_scratch;           // upe_gpu_rx_dispatch: the passes' tile table (upe_rx.hip)
+    DevBuf<uint8_t> eg_scratch;           // upe_gpu_egress_pack: the tile table (upe_egress.hip)
+    // upe_gpu_process_segmented scratch: marks / index per packet, gathered windows per mark
+    DevBuf<uint32_t> ctrl_marks, ctrl_index;
+    DevBuf<uint64_t> ctrl_count;
+    DevBuf<uint8_t> ctrl_win;
+    DevBuf<uint32_t> ctrl_lens;
     // neighbour tables (reachable-entry indexes)
-    uint4* arp = nullptr;
+    DevBuf<uint4> arp;
     uint32_t arp_bits = 0, arp_seed = 0;
-    uint4* ndp = nullptr;
+    DevBuf<uint4> ndp;
     uint32_t ndp_bits = 0, ndp_seed = 0;
     // state: one DevState allocation (see "Sequential state between batches")
-    DevState* st = nullptr;
+    DevBuf<DevState> st;
     uint64_t k = 0;                // launches so far: the next batch is batch k
     uint32_t last_n = 0;           // the last batch's size (batch_info)
-    unsigned long long* stats = nullptr;   // [cap][2]
-    TilePay* pay = nullptr;        // [2][paycap] per-workgroup last-hit payloads, by batch parity
+    DevBuf<unsigned long long> stats;   // [cap][2]
+    DevBuf<TilePay> pay;           // [2][paycap] per-workgroup last-hit payloads, by batch parity
     uint32_t paycap = 0;           // largest grid
-    // per-batch scratch
-    uint32_t* lb = nullptr;        // [tiles_alloc * kWaves] look-back flags (zeroed at allocation)
-    uint32_t* defer = nullptr;     // [64 * tiles_alloc * kWaves] deferred look-back candidates
-    size_t tiles_alloc = 0;
+    // per-batch scratch, for tiles of kWaves chunks
+    DevBuf<uint32_t> lb;           // a look-back flag per chunk (zeroed at allocation)
+    DevBuf<uint32_t> defer;        // 64 deferred look-back candidates (two words each) per chunk
     uint32_t lb_spin = 5000;       // look-back wait before deferring (UPE_GPU_LB_SPIN, 100 MHz ticks)
     bool lb_sync = false;          // UPE_GPU_LB_SYNC=1: wait for each launch's agreement report
     bool allow_nolb = true;        // UPE_GPU_NOLB=0: never use the kernels without look-back
     int last_var = -1;             // kernel variant of the last classify launch
     uint32_t last_grid = 0;
-    unsigned long long* ring_wg = nullptr;   // ring launches: per-batch counters + time origin
-    size_t ring_alloc = 0;
+    DevBuf<unsigned long long> ring_wg;   // ring launches: per-batch counters + time origin
     // every launch and state upload is ordered after the previous one, whatever its stream
     hipStream_t last_stream = nullptr;
     hipEvent_t order_ev = nullptr;
@@ -2556,12 +2547,10 @@ struct upe_gpu_ctx {
     // host round trip (upe_gpu_process_host): copy streams and three device slots
     hipStream_t s_in = nullptr, s_out = nullptr;
     struct HostSlot {
-        uint8_t* frames = nullptr;
-        size_t frames_cap = 0;
-        uint64_t* desc = nullptr;
-        uint32_t* verdict = nullptr;
-        upe_hdr_rec_t* hdr = nullptr;   // emit-mode records (upe_gpu_process_host_emit)
-        size_t pk_cap = 0;
+        DevBuf<uint8_t> frames;
+        DevBuf<uint64_t> desc;          // desc, verdict (and hdr, once used) hold as many packets
+        DevBuf<uint32_t> verdict;
+        DevBuf<upe_hdr_rec_t> hdr;      // emit-mode records (upe_gpu_process_host_emit)
         hipEvent_t in_done = nullptr, k_done = nullptr, out_done = nullptr;
         bool busy = false;
         uint64_t lo = 0, wb = 0;   // host byte range the slot's copy-back writes
@@ -2594,24 +2583,19 @@ int publish(upe_gpu_ctx* c) {
     } p = {c->pay, c->lb, c->stats, c->stats_idx};
     static_assert(offsetof(DevState, stats_idx) - offsetof(DevState, pay) == 3 * sizeof(void*),
                   "DevState pointer block");
-    HIP_TRY(hipMemcpy(reinterpret_cast<char*>(c->st) + offsetof(DevState, pay), &p, sizeof p,
+    HIP_TRY(hipMemcpy(reinterpret_cast<char*>(c->st.p) + offsetof(DevState, pay), &p, sizeof p,
                       hipMemcpyHostToDevice));
     return 0;
 }
 
 int ensure_scratch(upe_gpu_ctx* c, size_t ntiles) {
-    if (ntiles > c->tiles_alloc) {
-        if (c->lb) (void)hipFree(c->lb);
-        if (c->defer) (void)hipFree(c->defer);
-        c->lb = nullptr;
-        c->defer = nullptr;
-        c->tiles_alloc = 0;
-        size_t want = ntiles + ntiles / 4 + 16;
-        HIP_TRY(hipMalloc(&c->lb, want * kWaves * sizeof(uint32_t)));
-        HIP_TRY(hipMemset(c->lb, 0, want * kWaves * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&c->defer, 2 * 64 * want * kWaves * sizeof(uint32_t)));
-        c->tiles_alloc = want;
-        if (publish(c) != 0) return -1;
+    if (2 * 64 * ntiles * kWaves > c->defer.cap) {   // (the last one made)
+        c->lb.reset();   // both go before either comes back
+        c->defer.reset();
+        const size_t chunks = (ntiles + ntiles / 4 + 16) * kWaves;
+        if (c->lb.zeros(chunks) != 0 || c->defer.reserve(2 * 64 * chunks, 2 * 64 * chunks) != 0 ||
+            publish(c) != 0)
+            return -1;
     }
     return 0;
 }
@@ -2890,10 +2874,15 @@ upe_gpu_ctx_t* upe_gpu_open(int device, size_t rule_capacity) {
     }
     c->device = device;
     c->cap = rule_capacity;
+    auto failed = [&]() {   // the message is the failed step's
+        const std::string m = g_err;
+        upe_gpu_close(c);
+        g_err = m;
+        return nullptr;
+    };
     auto bad = [&](hipError_t e, const char* what) {
         fail(std::string(what) + ": " + hipGetErrorString(e));
-        upe_gpu_close(c);
-        return nullptr;
+        return failed();
     };
     DevScope dg(device);
     hipError_t e;
@@ -2902,10 +2891,8 @@ upe_gpu_ctx_t* upe_gpu_open(int device, size_t rule_capacity) {
         return bad(e, "hipStreamCreate");
     if ((e = hipEventCreateWithFlags(&c->order_ev, hipEventDisableTiming)) != hipSuccess)
         return bad(e, "hipEventCreate");
-    if ((e = hipMalloc(&c->st, sizeof(DevState))) != hipSuccess) return bad(e, "hipMalloc state");
-    if ((e = hipMemset(c->st, 0, sizeof(DevState))) != hipSuccess) return bad(e, "hipMemset");
-    if ((e = hipMalloc(&c->stats, rule_capacity * 2 * sizeof(unsigned long long))) != hipSuccess)
-        return bad(e, "hipMalloc stats");
+    if (c->st.zeros(1) != 0 || c->stats.reserve(rule_capacity * 2, rule_capacity * 2) != 0)
+        return failed();
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) ==
@@ -2923,10 +2910,7 @@ upe_gpu_ctx_t* upe_gpu_open(int device, size_t rule_capacity) {
     }
     // payload slots for the largest grid a launch uses (at most 8 workgroups per CU)
     c->paycap = 8u * (uint32_t)c->cus;
-    if ((e = hipMalloc(&c->pay, 2 * (size_t)c->paycap * sizeof(TilePay))) != hipSuccess)
-        return bad(e, "hipMalloc payloads");
-    if ((e = hipMemset(c->pay, 0, 2 * (size_t)c->paycap * sizeof(TilePay))) != hipSuccess)
-        return bad(e, "hipMemset");
+    if (c->pay.zeros(2 * (size_t)c->paycap) != 0) return failed();
     // host-mapped report of each launch's start-state agreement (the kernel without look-back
     // is used once one arrives; without it, every launch keeps the look-back)
     if (hipHostMalloc(reinterpret_cast<void**>(&c->agree_h), sizeof(unsigned long long),
@@ -2941,28 +2925,13 @@ upe_gpu_ctx_t* upe_gpu_open(int device, size_t rule_capacity) {
     } else {
         c->agree_h = nullptr;
     }
-    if (arm_state(c) != 0) {
-        std::string m = g_err;
-        upe_gpu_close(c);
-        g_err = m;
-        return nullptr;
-    }
+    if (arm_state(c) != 0) return failed();
     if ((e = hipMemsetAsync(c->stats, 0, rule_capacity * 2 * sizeof(unsigned long long),
                             c->stream)) != hipSuccess)
         return bad(e, "hipMemsetAsync");
     // An empty rule table: one padding block of never-matching rules.
-    if (upe_gpu_load_rules(c, nullptr, 0) != 0) {
-        std::string m = g_err;
-        upe_gpu_close(c);
-        g_err = m;
-        return nullptr;
-    }
-    if (upe_gpu_load_neigh(c, nullptr, 0, nullptr, 0) != 0 || refresh(c) != 0) {
-        std::string m = g_err;
-        upe_gpu_close(c);
-        g_err = m;
-        return nullptr;
-    }
+    if (upe_gpu_load_rules(c, nullptr, 0) != 0) return failed();
+    if (upe_gpu_load_neigh(c, nullptr, 0, nullptr, 0) != 0 || refresh(c) != 0) return failed();
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return bad(e, "sync");
     return c;
 }
@@ -2971,30 +2940,18 @@ void upe_gpu_close(upe_gpu_ctx_t* c) {
     if (!c) return;
     DevScope dg(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    void* bufs[] = {c->rv4, c->rv6, c->rinfo, c->stats_idx, c->gb, c->arp, c->ndp, c->st, c->stats,
-                    c->pay, c->lb, c->tg4, c->tg6, c->tt4, c->tt6, c->tfs, c->fam, c->tree,
-                    c->compact_counts, c->rx_scratch, c->eg_scratch,
-                    c->ctrl_marks, c->ctrl_index, c->ctrl_count, c->ctrl_win, c->ctrl_lens,
-                    c->hist_part};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (c->defer) (void)hipFree(c->defer);
-    if (c->ring_wg) (void)hipFree(c->ring_wg);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
     if (c->order_ev) (void)hipEventDestroy(c->order_ev);
     for (hipEvent_t e : c->marks)
         if (e) (void)hipEventDestroy(e);
-    for (auto& sl : c->hs) {
-        for (void* b : {(void*)sl.frames, (void*)sl.desc, (void*)sl.verdict, (void*)sl.hdr})
-            if (b) (void)hipFree(b);
+    for (auto& sl : c->hs)
         for (hipEvent_t e : {sl.in_done, sl.k_done, sl.out_done})
             if (e) (void)hipEventDestroy(e);
-    }
     if (c->s_in) (void)hipStreamSynchronize(c->s_in), (void)hipStreamDestroy(c->s_in);
     if (c->s_out) (void)hipStreamSynchronize(c->s_out), (void)hipStreamDestroy(c->s_out);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->agree_h) (void)hipHostFree(c->agree_h);
-    delete c;
+    delete c;   // the device buffers go with it (DevBuf), on the context's device
 }
 
 namespace {
@@ -3067,44 +3024,13 @@ int read_rule_stats(upe_gpu_ctx* c, upe_rule_stat_t* rule_stats, size_t capacity
 }  // extern "C"
 
 namespace {
-// A device allocation that frees itself unless taken: load_rules uploads every image of the new
-// table first and changes the context only once all of them are on the device.
-struct DevBuf {
-    void* p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    int put(const void* src, size_t bytes) {
-        if (bytes == 0) return 0;
-        HIP_TRY(hipMalloc(&p, bytes));
-        HIP_TRY(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
-        return 0;
-    }
-    template <class T>
-    T* take() {
-        T* q = static_cast<T*>(p);
-        p = nullptr;
-        return q;
-    }
-};
-template <class T>
-void replace(T*& field, DevBuf& b) {
-    if (field) (void)hipFree(field);
-    field = b.take<T>();
-}
-
-}  // namespace
-
-namespace {
+using StatsBuf = DevBuf<unsigned long long>;
 // upe_gpu_load_rules / upe_gpu_reload_rules[_image] with a compiled image: `fresh` (a zeroed
 // rule_stats of fresh_cap entries) replaces the context's statistics on a reload, the old
 // per-index totals dropped instead of credited.  Everything the new table needs is uploaded
 // before the context changes: on an error the context keeps classifying with the old table and
 // its statistics.
-int install_image(upe_gpu_ctx_t* c, const upe_rule_image& im, DevBuf* fresh, size_t fresh_cap) {
+int install_image(upe_gpu_ctx_t* c, const upe_rule_image& im, StatsBuf* fresh, size_t fresh_cap) {
     const size_t count = im.count, pad = im.pad;
     const std::vector<RuleV4>& v4 = im.v4;
     const std::vector<RuleV6>& v6 = im.v6;
@@ -3118,50 +3044,47 @@ int install_image(upe_gpu_ctx_t* c, const upe_rule_image& im, DevBuf* fresh, siz
     const TreeImage& t = im.t;
     const uint32_t fam4 = im.fam4, fam6 = im.fam6, fam_all = im.fam_all, fam_x1idx = im.fam_x1idx;
     const bool fwd4 = im.fwd4, fwd6 = im.fwd6;
-    // every image on the device before anything of the context changes
-    DevBuf b_rv4, b_rv6, b_rinfo, b_idx, b_fam, b_tfs, b_tg4, b_tg6, b_tt4, b_tt6, b_tree;
-    if (b_rv4.put(v4.data(), pad * sizeof(RuleV4)) || b_rv6.put(v6.data(), pad * sizeof(RuleV6)) ||
-        b_rinfo.put(info.data(), pad * sizeof(int2)) ||
-        b_fam.put(fimg.data(), fimg.size() * sizeof(uint4)) ||
-        (tss && (b_tfs.put(fps.data(), fps.size() * sizeof(uint16_t)) ||
-                 b_tg4.put(f4.groups.data(), f4.groups.size() * sizeof(TssGroup)) ||
-                 b_tg6.put(f6.groups.data(), f6.groups.size() * sizeof(TssGroup)) ||
-                 b_tt4.put(f4.slots.data(), f4.slots.size() * sizeof(uint4)) ||
-                 b_tt6.put(f6.slots.data(), f6.slots.size() * sizeof(uint4)))) ||
-        (tree_ok && b_tree.put(timg.data(), timg.size() * sizeof(uint4))))
+    // every image on the device before anything of the context changes (what is not taken over
+    // below is freed on return)
+    DevBuf<RuleV4> b_rv4;
+    DevBuf<RuleV6> b_rv6;
+    DevBuf<int2> b_rinfo;
+    DevBuf<uint4> b_fam, b_tt4, b_tt6, b_tree;
+    DevBuf<uint16_t> b_tfs;
+    DevBuf<TssGroup> b_tg4, b_tg6;
+    StatsBuf b_idx;
+    if (b_rv4.put(v4.data(), pad) || b_rv6.put(v6.data(), pad) || b_rinfo.put(info.data(), pad) ||
+        b_fam.put(fimg.data(), fimg.size()) ||
+        (tss && (b_tfs.put(fps.data(), fps.size()) ||
+                 b_tg4.put(f4.groups.data(), f4.groups.size()) ||
+                 b_tg6.put(f6.groups.data(), f6.groups.size()) ||
+                 b_tt4.put(f4.slots.data(), f4.slots.size()) ||
+                 b_tt6.put(f6.slots.data(), f6.slots.size()))) ||
+        (tree_ok && b_tree.put(timg.data(), timg.size())))
         return -1;
-    const bool grow = pad > c->rules_alloc;
-    if (grow) {
-        const size_t bytes = pad * 2 * kStatReps * sizeof(unsigned long long);
-        HIP_TRY(hipMalloc(&b_idx.p, bytes));
-        HIP_TRY(hipMemset(b_idx.p, 0, bytes));
-    }
+    // the per-index totals are kept while they hold the new table
+    const bool grow = pad * 2 * kStatReps > c->stats_idx.cap;
+    if (grow && b_idx.zeros(pad * 2 * kStatReps) != 0) return -1;
     // previous batches may still read the table, on whichever stream they went
     if (c->last_stream) HIP_TRY(hipStreamSynchronize(c->last_stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (fresh) {
         // the reload's fresh statistics: the old table's per-index totals are dropped
         if (c->stats_idx)
-            HIP_TRY(hipMemset(c->stats_idx, 0,
-                              (size_t)c->rules_alloc * 2 * kStatReps * sizeof(unsigned long long)));
+            HIP_TRY(hipMemset(c->stats_idx, 0, c->stats_idx.cap * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(&c->st->acc_stats[0][0], 0, sizeof(c->st->acc_stats)));
-        if (c->stats) (void)hipFree(c->stats);
-        c->stats = fresh->take<unsigned long long>();
+        c->stats = std::move(*fresh);
         c->cap = fresh_cap;
         c->rinfo_host.clear();
     } else if (fold_stats_idx(c) != 0) {   // the old table's counts credited to their rule_ids
         return -1;
     }
-    // the swap
-    replace(c->rv4, b_rv4);
-    replace(c->rv6, b_rv6);
-    replace(c->rinfo, b_rinfo);
-    if (grow) {
-        replace(c->stats_idx, b_idx);
-        c->rules_alloc = pad;
-    }
-    replace(c->fam, b_fam);
-    c->fam_alloc = fimg.size() * sizeof(uint4);
+    // the swap (each move frees what the context held)
+    c->rv4 = std::move(b_rv4);
+    c->rv6 = std::move(b_rv6);
+    c->rinfo = std::move(b_rinfo);
+    if (grow) c->stats_idx = std::move(b_idx);
+    c->fam = std::move(b_fam);
     c->fam4 = fam4;
     c->fam6 = fam6;
     c->fam_all = fam_all;
@@ -3175,16 +3098,16 @@ int install_image(upe_gpu_ctx_t* c, const upe_rule_image& im, DevBuf* fresh, siz
     c->nrules = (uint32_t)count;
     c->nrules_pad = (uint32_t)pad;
     c->rinfo_host = info;
-    replace(c->tfs, b_tfs);
-    replace(c->tg4, b_tg4);
-    replace(c->tg6, b_tg6);
-    replace(c->tt4, b_tt4);
-    replace(c->tt6, b_tt6);
+    c->tfs = std::move(b_tfs);
+    c->tg4 = std::move(b_tg4);
+    c->tg6 = std::move(b_tg6);
+    c->tt4 = std::move(b_tt4);
+    c->tt6 = std::move(b_tt6);
     c->tss = tss;
     c->nfs = tss ? (uint32_t)(fps.size() / 8) : 0u;
     c->ng4 = tss ? (uint32_t)f4.groups.size() : 0u;
     c->ng6 = tss ? (uint32_t)f6.groups.size() : 0u;
-    replace(c->tree, b_tree);
+    c->tree = std::move(b_tree);
     c->tree_ok = tree_ok;
     const char* tl = getenv("UPE_GPU_TREE_LDS");   // diagnostic: 0 = the image stays in memory
     c->tree_stage = !(tl && tl[0] == '0');
@@ -3198,7 +3121,7 @@ int install_image(upe_gpu_ctx_t* c, const upe_rule_image& im, DevBuf* fresh, siz
 }
 
 int load_rules_impl(upe_gpu_ctx_t* c, const upe_rule_t* rules, size_t count,
-                    DevBuf* fresh, size_t fresh_cap) {
+                    StatsBuf* fresh, size_t fresh_cap) {
     upe_rule_image im;
     if (build_image(rules, count, fresh ? fresh_cap : c->cap, im) != 0) return -1;
     return install_image(c, im, fresh, fresh_cap);
@@ -3239,9 +3162,8 @@ extern "C" int upe_gpu_reload_rules(upe_gpu_ctx_t* c, const upe_rule_t* rules, s
     if (c->last_stream) HIP_TRY(hipStreamSynchronize(c->last_stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (old_capacity && read_rule_stats(c, old_stats, old_capacity) != 0) return -1;
-    DevBuf fresh;   // a zeroed rule_stats of the new capacity (freed unless the reload succeeds)
-    HIP_TRY(hipMalloc(&fresh.p, rule_capacity * 2 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(fresh.p, 0, rule_capacity * 2 * sizeof(unsigned long long)));
+    StatsBuf fresh;   // a zeroed rule_stats of the new capacity (freed unless the reload succeeds)
+    if (fresh.zeros(rule_capacity * 2) != 0) return -1;
     return load_rules_impl(c, rules, count, &fresh, rule_capacity);
 }
 
@@ -3253,9 +3175,8 @@ extern "C" int upe_gpu_reload_image(upe_gpu_ctx_t* c, const upe_rule_image_t* im
     if (c->last_stream) HIP_TRY(hipStreamSynchronize(c->last_stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (old_capacity && read_rule_stats(c, old_stats, old_capacity) != 0) return -1;
-    DevBuf fresh;
-    HIP_TRY(hipMalloc(&fresh.p, im->cap * 2 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(fresh.p, 0, im->cap * 2 * sizeof(unsigned long long)));
+    StatsBuf fresh;
+    if (fresh.zeros(im->cap * 2) != 0) return -1;
     return install_image(c, *im, &fresh, im->cap);
 }
 
@@ -3351,11 +3272,10 @@ int upe_gpu_load_neigh(upe_gpu_ctx_t* c, const upe_arp_entry_t* arp, size_t arp_
     if (c->st && l1_sync(c) != 0) return -1;
     if (c->last_stream) HIP_TRY(hipStreamSynchronize(c->last_stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->arp) (void)hipFree(c->arp);
-    if (c->ndp) (void)hipFree(c->ndp);
-    c->arp = nullptr; c->ndp = nullptr;
-    HIP_TRY(hipMalloc(&c->arp, a.size() * sizeof(uint4)));
-    HIP_TRY(hipMalloc(&c->ndp, b.size() * sizeof(uint4)));
+    c->arp.reset();   // both go before either comes back
+    c->ndp.reset();
+    if (c->arp.reserve(a.size(), a.size()) != 0 || c->ndp.reserve(b.size(), b.size()) != 0)
+        return -1;
     HIP_TRY(hipMemcpy(c->arp, a.data(), a.size() * sizeof(uint4), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->ndp, b.data(), b.size() * sizeof(uint4), hipMemcpyHostToDevice));
     c->arp_bits = abits;
@@ -3425,70 +3345,93 @@ struct RingReq {
     size_t per;
     unsigned long long* done;   // [count] ns after the first workgroup's start, 0 = not stamped
 };
-int process_impl(upe_gpu_ctx_t* c, uint8_t* d_frames, const uint64_t* d_desc, uint32_t* d_verdict,
-                 uint32_t* d_flow_hash, upe_hdr_rec_t* d_hdr, size_t n, void* stream,
-                 const RingReq* ring = nullptr, bool host = false, uint32_t* d_tx = nullptr,
-                 uint32_t* d_tx_cnt = nullptr, size_t tx_base = 0) {
-    if (!c) return fail("null context");
-    host = host || c->host_tag;
-    if (n > 0xFFFFFFFFull - kTile) return fail("batch too large (n must fit in 32 bits)");
-    if (n && (!d_frames || !d_desc || !d_verdict)) return fail("null batch buffer");
-    if (((uintptr_t)d_frames & 15u) != 0) return fail("frames buffer must be 16-byte aligned");
-    if (((uintptr_t)d_hdr & 15u) != 0) return fail("header records must be 16-byte aligned");
-    if (ring && n > kMaxLaunch) return fail("a ring holds at most 2^24 packets");
-    if (n > kMaxLaunch) {
-        // consecutive launches of at most kMaxLaunch packets: the worker's stream semantics are
-        // those of one batch (batch_info describes the last launch)
-        for (size_t s0 = 0; s0 < n; s0 += kMaxLaunch) {
-            const size_t m = n - s0 < kMaxLaunch ? n - s0 : kMaxLaunch;
-            if (process_impl(c, d_frames, d_desc + s0, d_verdict + s0,
-                             d_flow_hash ? d_flow_hash + s0 : nullptr, d_hdr ? d_hdr + s0 : nullptr,
-                             m, stream, nullptr, host, d_tx ? d_tx + s0 : nullptr,
-                             d_tx_cnt ? d_tx_cnt + s0 / 64 : nullptr, tx_base + s0) != 0)
-                return -1;
-        }
-        return 0;
-    }
-    DEV_SCOPE(c->device);
-    hipStream_t s = pick(c, stream);
-    const uint32_t ntiles = (uint32_t)((n + kTile - 1) / kTile);
-    if (ensure_scratch(c, ntiles ? ntiles : 1) != 0) return -1;
-    // after the context's previous launch and its own uploads (tables, L1), on whichever stream
-    // they went: a batch starts from the state the one before it left
-    if (order_on(c, s) != 0) return -1;
-    // timing sample: an event pair around `timing_span` consecutive calls, opened on every
-    // timing_every-th call (samples never overlap)
+// One request to process_impl: a batch in device-visible memory, and what is wanted beside the
+// verdicts.
+struct ProcessReq {
+    uint8_t* frames;
+    const uint64_t* desc;
+    uint32_t* verdict;
+    size_t n;
+    void* stream;
+    upe_hdr_rec_t* hdr = nullptr;    // emit mode: [n] rewritten-header records, frames only read
+    uint32_t* flow_hash = nullptr;   // [n] flow hashes (RSS)
+    const RingReq* ring = nullptr;   // the batch is a ring of batches
+    bool host = false;               // launched for a host path (Path::Host)
+    uint32_t* tx = nullptr;          // the egress list (Path::Tx) and its per-group counts
+    uint32_t* tx_cnt = nullptr;
+    size_t tx_base = 0;              // the launch's first packet in the caller's batch
+};
+
+TableShape table_shape(const upe_gpu_ctx* c) {
+    return TableShape{c->tss, c->nrules, c->nrules_pad, c->arp_bits, c->ndp_bits, c->nfs,
+                      c->tree_ok, c->tree_stage, c->tree_words, c->fam4, c->fam6, c->fam_all != 0};
+}
+
+// Timing sample: an event pair around `timing_span` consecutive calls, opened on every
+// timing_every-th call (samples never overlap).
+int open_sample(upe_gpu_ctx* c, hipStream_t s) {
     const bool open = c->timing && c->t_left == 0 &&
                       (c->timing_calls % c->timing_every) == c->timing_phase;
     if (c->timing) ++c->timing_calls;
-    if (open) {
-        while (c->ev.size() < c->ev_used + 3) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreate(&e));
-            c->ev.push_back(e);
-        }
-        HIP_TRY(hipEventRecord(c->ev[c->ev_used], s));
-        c->t_left = c->timing_span;
+    if (!open) return 0;
+    while (c->ev.size() < c->ev_used + 3) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreate(&e));
+        c->ev.push_back(e);
     }
+    HIP_TRY(hipEventRecord(c->ev[c->ev_used], s));
+    c->t_left = c->timing_span;
+    return 0;
+}
+// mid: the sample's middle event was recorded (mid_sample)
+int close_sample(upe_gpu_ctx* c, hipStream_t s, bool mid) {
+    if (c->t_left && --c->t_left == 0) {
+        HIP_TRY(hipEventRecord(c->ev[c->ev_used + 2], s));
+        c->ev_mid.push_back(mid);
+        c->ev_used += 3;
+        c->timing_launches += c->timing_span;
+    }
+    return 0;
+}
+
+// Once a launch has been seen starting from agreeing L1 entries (or from an entry whose
+// family's index is empty), every later one does until the host changes tables or entries:
+// c->no_lb.
+int settle_no_lb(upe_gpu_ctx* c) {
+    if (c->no_lb || !c->agree_h || !c->allow_nolb) return 0;
+    if (c->lb_sync && c->k > c->lb_reset_k && c->last_stream)
+        HIP_TRY(hipStreamSynchronize(c->last_stream));   // the previous launch's report
+    const unsigned long long v = __atomic_load_n(c->agree_h, __ATOMIC_ACQUIRE);
+    const unsigned long long tag = v >> 2;
+    if (tag != 0 && tag - 1 >= c->lb_reset_k && ((v & 1) || c->arp_bits == 0 || !c->fwd4) &&
+        ((v & 2) || c->ndp_bits == 0 || !c->fwd6))
+        c->no_lb = true;
+    return 0;
+}
+
+// The kernel's arguments but for the tiling and the ring's (process_impl sets those).
+Args fill_args(const upe_gpu_ctx* c, const ProcessReq& q, const LdsPlan& p) {
     Args a;
     memset(&a, 0, sizeof a);   // every field a launch does not set stays null / zero
-    a.frames = d_frames;
-    a.desc = d_desc;
-    a.verdict = d_verdict;
-    a.n = (uint32_t)n;
-    a.tx = d_tx;
-    a.tx_cnt = d_tx_cnt;
-    a.tx_base = (uint32_t)tx_base;
+    a.frames = q.frames;
+    a.desc = q.desc;
+    a.verdict = q.verdict;
+    a.n = (uint32_t)q.n;
+    a.tx = q.tx;
+    a.tx_cnt = q.tx_cnt;
+    a.tx_base = (uint32_t)q.tx_base;
+    a.flow_hash = q.flow_hash;
+    a.hdr = reinterpret_cast<uint4*>(q.hdr);
     a.rv4 = c->rv4;
     a.rv6 = c->rv6;
+    a.rinfo = c->rinfo;
+    a.nrules_pad = c->nrules_pad;
     a.fam = c->fam;
     a.fam4 = c->fam4;
     a.fam6 = c->fam6;
     a.fam_x1idx = c->fam_x1idx;
-    a.tree = reinterpret_cast<const uint2*>(c->tree);
+    a.tree = reinterpret_cast<const uint2*>(c->tree.p);
     a.tree_loff = c->tree_loff;
-    a.rinfo = c->rinfo;
-    a.nrules_pad = c->nrules_pad;
     a.arp = arp_index(c);
     a.ndp = ndp_index(c);
     a.st = c->st;
@@ -3499,207 +3442,156 @@ int process_impl(upe_gpu_ctx_t* c, uint8_t* d_frames, const uint64_t* d_desc, ui
     a.tg6 = c->tg6;
     a.tt4 = c->tt4;
     a.tt6 = c->tt6;
-    a.tfs = reinterpret_cast<const uint4*>(c->tfs);
+    a.tfs = reinterpret_cast<const uint4*>(c->tfs.p);
     a.ng4 = c->ng4;
     a.ng6 = c->ng6;
     a.tss = c->tss ? 1u : 0u;
     a.pay = c->pay;
     a.paycap = c->paycap;
+    a.stats = c->stats;
+    a.stats_idx = c->stats_idx;
     a.k6 = (uint32_t)(c->k % 6);
     a.lb = c->lb;
     a.defer = c->defer;
     a.lb_spin = c->lb_spin;
     a.lb_tag = (uint32_t)(c->k % kLbTagMod) + 1u;
-    if (c->k > 0 && c->k % kLbTagMod == 0)   // tags wrap: no flag may carry this launch's tag
-        HIP_TRY(hipMemsetAsync(c->lb, 0, c->tiles_alloc * kWaves * sizeof(uint32_t), s));
-    a.stats = c->stats;
-    a.stats_idx = c->stats_idx;
-    a.flow_hash = d_flow_hash;
-    a.hdr = reinterpret_cast<uint4*>(d_hdr);
-    const bool emit = d_hdr != nullptr && n > 0;
-    const bool lds_stats = c->nrules_pad <= (uint32_t)kLdsStatsMax;
-    a.gb = nullptr;
-    a.gb_packed = c->nrules <= 65536u ? 1u : 0u;   // sorted indexes of matches < nrules
-    if (!lds_stats && n > 0) {
-        if (n > c->gb_alloc) {
-            if (c->gb) (void)hipFree(c->gb);
-            c->gb = nullptr;
-            c->gb_alloc = 0;
-            const size_t want = (n + n / 4 + 64) & ~(size_t)3;
-            HIP_TRY(hipMalloc(&c->gb, want * sizeof(uint32_t)));   // room for either form
-            c->gb_alloc = want;
-        }
-        a.gb = c->gb;
-    }
-    const size_t hist = lds_stats ? 2 * (size_t)c->nrules_pad * sizeof(uint32_t) : 0;
-    // large linear tables: the decision tree (when built), else family lists, unless a family's
-    // list is a single catch-all (then the split gains that family nothing and measured slower
-    // for the other)
-    const int scan = c->tss || c->nrules_pad <= (uint32_t)kSmallRules ? 0
-                   : c->tree_ok ? 3 : c->fam_all ? 2 : 1;
-    const size_t lds_max = scan ? kLdsDynMaxLarge : kLdsDynMax;
-    // stage the ARP index in LDS when it is small (the nrules_pad multiple of 4 keeps the slot
-    // array 16-byte aligned after the bins)
-    const uint32_t arp_slots = c->arp_bits ? (1u << c->arp_bits) : 0u;
-    const uint32_t ndp_slots = c->ndp_bits ? (1u << c->ndp_bits) : 0u;
-    size_t lds = hist;
-    a.arp_lds = a.ndp_lds = 0u;
-    if (arp_slots && arp_slots <= kArpLdsSlots && lds + arp_slots * sizeof(uint4) <= lds_max) {
-        a.arp_lds = arp_slots;
-        lds += arp_slots * sizeof(uint4);
-    }
-    if (ndp_slots && ndp_slots <= kNdpLdsSlots && lds + 2 * ndp_slots * sizeof(uint4) <= lds_max) {
-        a.ndp_lds = ndp_slots;
-        lds += 2 * ndp_slots * sizeof(uint4);
-    }
-    a.fp_lds = 0u;
-    if (c->tss && c->nfs && lds + c->nfs * sizeof(uint4) <= lds_max) {
-        a.fp_lds = c->nfs;
-        lds += c->nfs * sizeof(uint4);
-    }
-    // the tree's image in LDS first (every lane reads a node per level), then the IPv6 list
-    a.tree_lds = 0u;
-    if (scan == 3 && c->tree_stage && lds + c->tree_words * sizeof(uint4) <= lds_max) {
-        a.tree_lds = c->tree_words;
-        lds += c->tree_words * sizeof(uint4);
-    }
-    a.fam6_lds = 0u;
-    if (kFamLds && !c->tss && (scan == 3 || !c->fam_all) && c->fam6 &&
-        lds + kFamV6Stride * c->fam6 * sizeof(uint4) <= lds_max) {
-        a.fam6_lds = 1u;
-        lds += kFamV6Stride * c->fam6 * sizeof(uint4);
-    }
-    // the tree kernels' leaf tests read the IPv4 list's rule words too: from LDS when it fits
-    a.fam4_lds = 0u;
-    if (scan == 3 && c->tree_stage && c->fam4 && lds + 2 * c->fam4 * sizeof(uint4) <= lds_max) {
-        a.fam4_lds = 1u;
-        lds += 2 * c->fam4 * sizeof(uint4);
-    }
-    // the lean emit kernel when nothing it leaves out is needed (non-empty neighbour indexes
-    // all in LDS, no flow_hash, no length side array)
-    const bool lean = !d_flow_hash && (c->tss || !a.gb) &&
-                      (arp_slots == 0 || a.arp_lds != 0) && (ndp_slots == 0 || a.ndp_lds != 0);
-    // once a launch has been seen starting from agreeing L1 entries (or from an entry whose
-    // family's index is empty), every later one does until the host changes tables or entries
-    if (!c->no_lb && c->agree_h && c->allow_nolb) {
-        if (c->lb_sync && c->k > c->lb_reset_k && c->last_stream)
-            HIP_TRY(hipStreamSynchronize(c->last_stream));   // the previous launch's report
-        const unsigned long long v = __atomic_load_n(c->agree_h, __ATOMIC_ACQUIRE);
-        const unsigned long long tag = v >> 2;
-        if (tag != 0 && tag - 1 >= c->lb_reset_k && ((v & 1) || c->arp_bits == 0 || !c->fwd4) &&
-            ((v & 2) || c->ndp_bits == 0 || !c->fwd6))
-            c->no_lb = true;
-    }
     a.agree_out = c->no_lb ? nullptr : c->agree_d;
     a.launch_tag = c->k + 1;
-    // a ring launch stamps its batches' completion with the ring kernels (lean emit linear scan)
-    // (at most kRingMax batches: one LDS counter each)
-    bool stamp = ring && ring->done && emit && lean && !c->tss && n / ring->per <= (size_t)kRingMax;
-    // (the egress list: emit, device batches, never a ring: upe_gpu_process_emit_tx)
-    const bool tx = d_tx != nullptr;
-    Variant var{c->tss, emit, lean, lean && c->no_lb,
-                tx ? Path::Tx : stamp ? Path::Ring : host ? Path::Host : Path::Device, scan};
-    // persistent grid: the workgroups the chip holds at once (or one per tile if fewer)
-    uint32_t grid_cap = resident_grid(c, var, lds, s);
+    // the plan's share (upe_plan.h)
+    a.gb = p.gb ? c->gb.p : nullptr;
+    a.gb_packed = p.gb_packed;
+    a.arp_lds = p.arp_lds;
+    a.ndp_lds = p.ndp_lds;
+    a.fp_lds = p.fp_lds;
+    a.tree_lds = p.tree_lds;
+    a.fam6_lds = p.fam6_lds;
+    a.fam4_lds = p.fam4_lds;
+    return a;
+}
+
+// The rule_stats group-by of a batch the classify launch left keys for (tables over
+// kLdsStatsMax rules): dense partials, one 8-byte bin per chunk and rule, summed by
+// upe_hist_reduce.
+int launch_group_by(upe_gpu_ctx* c, const uint32_t* d_verdict, size_t n, bool packed,
+                    hipStream_t s) {
+    const GroupByPlan g = plan_group_by(c->nrules, n);
+    const size_t part_words = (size_t)g.grid_x * g.nrules;
+    if (c->hist_part.reserve(part_words, part_words) != 0) return -1;
+    static std::atomic<uint64_t> hist_attr{0};   // 128 KB of dynamic LDS, once per device
+    if (!(hist_attr.fetch_or(1ull << (c->device & 63)) & (1ull << (c->device & 63)))) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&upe_rule_hist<true>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(kHistRange * sizeof(unsigned long long)));
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&upe_rule_hist<false>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(kHistRange * sizeof(unsigned long long)));
+    }
+    const dim3 hg(g.grid_x, g.nr);
+    const size_t lds = g.range * sizeof(unsigned long long);
+    if (packed)
+        hipLaunchKernelGGL(upe_rule_hist<true>, hg, dim3(kHistBlock), lds, s, d_verdict,
+                           c->gb.p, (uint32_t)n, g.nrules, c->hist_part.p, g.chunk, g.range);
+    else
+        hipLaunchKernelGGL(upe_rule_hist<false>, hg, dim3(kHistBlock), lds, s, d_verdict,
+                           c->gb.p, (uint32_t)n, g.nrules, c->hist_part.p, g.chunk, g.range);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(upe_hist_reduce, dim3((g.nrules + 255) / 256, kStatReps), dim3(256), 0, s,
+                       c->hist_part.p, g.grid_x, g.nrules, c->nrules_pad, c->stats_idx.p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int process_impl(upe_gpu_ctx_t* c, const ProcessReq& q) {
+    // 1. validate
+    if (!c) return fail("null context");
+    const size_t n = q.n;
+    const bool host = q.host || c->host_tag;
+    if (n > 0xFFFFFFFFull - kTile) return fail("batch too large (n must fit in 32 bits)");
+    if (n && (!q.frames || !q.desc || !q.verdict)) return fail("null batch buffer");
+    if (((uintptr_t)q.frames & 15u) != 0) return fail("frames buffer must be 16-byte aligned");
+    if (((uintptr_t)q.hdr & 15u) != 0) return fail("header records must be 16-byte aligned");
+    if (q.ring && n > kMaxLaunch) return fail("a ring holds at most 2^24 packets");
+    // 2. consecutive launches of at most kMaxLaunch packets: the worker's stream semantics are
+    // those of one batch (batch_info describes the last launch)
+    if (n > kMaxLaunch) {
+        for (size_t s0 = 0; s0 < n; s0 += kMaxLaunch) {
+            ProcessReq part = q;
+            part.desc += s0;
+            part.verdict += s0;
+            part.n = n - s0 < kMaxLaunch ? n - s0 : kMaxLaunch;
+            if (q.hdr) part.hdr += s0;
+            if (q.flow_hash) part.flow_hash += s0;
+            part.host = host;
+            if (q.tx) part.tx += s0;
+            if (q.tx_cnt) part.tx_cnt += s0 / 64;
+            part.tx_base = q.tx_base + s0;
+            if (process_impl(c, part) != 0) return -1;
+        }
+        return 0;
+    }
+    DEV_SCOPE(c->device);
+    hipStream_t s = pick(c, q.stream);
+    if (ensure_scratch(c, n ? (n + kTile - 1) / kTile : 1) != 0) return -1;
+    // 3. after the context's previous launch and its own uploads (tables, L1), on whichever stream
+    // they went: a batch starts from the state the one before it left
+    if (order_on(c, s) != 0 || open_sample(c, s) != 0) return -1;
+    if (c->k > 0 && c->k % kLbTagMod == 0)   // tags wrap: no flag may carry this launch's tag
+        HIP_TRY(hipMemsetAsync(c->lb, 0, c->lb.cap * sizeof(uint32_t), s));
+    // 4. plan (upe_plan.h)
+    if (settle_no_lb(c) != 0) return -1;
+    const bool emit = q.hdr != nullptr && n > 0;
+    const PlanReq pq{n, emit, q.flow_hash != nullptr, q.tx != nullptr, host,
+                     q.ring ? q.ring->per : 0, q.ring && q.ring->done};
+    const LdsPlan p = plan_lds(table_shape(c), pq, c->no_lb);
+    if (p.gb && c->gb.reserve(n, (n + n / 4 + 64) & ~(size_t)3) != 0) return -1;   // either form
+    // 5. the arguments
+    Args a = fill_args(c, q, p);
+    // persistent grid: the workgroups the chip holds at once
+    Variant var = p.var;
+    const uint32_t grid_cap = resident_grid(c, var, p.lds, s);
     if (grid_cap == 0) return -1;
     // the census of the no-look-back counterpart now as well, so that the switch to it (a few
     // launches later) does not put a synchronous census launch in the middle of a batch stream
-    if (lean && !c->no_lb) {
+    if (p.lean && !c->no_lb) {
         Variant nolb = var;
         nolb.nolb = true;
-        if (resident_grid(c, nolb, lds, s) == 0) return -1;
+        if (resident_grid(c, nolb, p.lds, s) == 0) return -1;
     }
-    // Tiles of kWaves chunks (one per wave of a workgroup); a batch too small to give every
-    // resident workgroup a tile gets narrower tiles, down to one chunk, so that it spreads over
-    // more CUs (a 10k-packet batch on ten CUs, four waves per SIMD, took 9.2 us; spread, 7.9).
-    const uint32_t nchunks = (uint32_t)((n + 63) / 64);
-    uint32_t tw = (uint32_t)kWaves;
-    while (tw > 1 && (nchunks + tw - 1) / tw < grid_cap) tw >>= 1;
-    a.tw = tw;
-    a.ntiles = (nchunks + tw - 1) / tw;
-    const uint32_t grid = a.ntiles == 0 ? 1u : a.ntiles < grid_cap ? a.ntiles : grid_cap;
-    if (ring && ring->done) {
-        HIP_TRY(hipMemsetAsync(ring->done, 0, (n / ring->per) * sizeof(unsigned long long), s));
-        // every workgroup must own the same number of tiles of every batch (at least one)
-        const size_t tpb = (ring->per / 64) / tw;
-        if (stamp && (tpb < grid || tpb % grid != 0)) stamp = false;
-        if (!stamp) {
-            var.path = Path::Device;
-            if (resident_grid(c, var, lds, s) == 0) return -1;
+    const Tiling t = plan_tiling(n, grid_cap);
+    a.tw = t.tw;
+    a.ntiles = t.ntiles;
+    // 6. a ring's stamps
+    if (pq.ring_done) {
+        const size_t nb = n / q.ring->per;
+        HIP_TRY(hipMemsetAsync(q.ring->done, 0, nb * sizeof(unsigned long long), s));
+        const RingPlan r = plan_ring(p, pq, t);
+        var = r.var;
+        if (!r.stamp) {
+            if (resident_grid(c, var, p.lds, s) == 0) return -1;
         } else {
-            const size_t nb = n / ring->per;
-            if (nb > c->ring_alloc) {
-                if (c->ring_wg) HIP_TRY(hipFree(c->ring_wg));
-                c->ring_wg = nullptr;
-                c->ring_alloc = 0;
-                HIP_TRY(hipMalloc(&c->ring_wg, (nb + 2) * sizeof(unsigned long long)));
-                c->ring_alloc = nb;
-            }
+            // the batches' counters, then the time origin
+            if (c->ring_wg.reserve(nb + 2, nb + 2) != 0) return -1;
             HIP_TRY(hipMemsetAsync(c->ring_wg, 0, nb * sizeof(unsigned long long), s));
             HIP_TRY(hipMemsetAsync(c->ring_wg + nb, 0xFF, sizeof(unsigned long long), s));
-            a.ring_cpb = (uint32_t)(ring->per / 64);
-            a.ring_mine = (uint32_t)(tpb / grid * tw);
-            a.ring_wg = reinterpret_cast<uint32_t*>(c->ring_wg);
-            a.ring_done = ring->done;
+            a.ring_cpb = r.ring_cpb;
+            a.ring_mine = r.ring_mine;
+            a.ring_wg = reinterpret_cast<uint32_t*>(c->ring_wg.p);
+            a.ring_done = q.ring->done;
             a.ring_t0 = c->ring_wg + nb;
         }
     }
-    launch_classify(var, grid, lds, s, a);
+    // 7. launch
+    launch_classify(var, t.grid, p.lds, s, a);
     HIP_TRY(hipGetLastError());
     c->last_var = (int)variant_word(var);
-    c->last_grid = grid;
-    const bool group_by = !lds_stats && n > 0;
-    // the sample's middle event, between the classify launch and the group-by (last call of the
-    // sample only; launches without a group-by have none)
-    const bool mid = c->t_left == 1 && group_by;
+    c->last_grid = t.grid;
+    // 8. the group-by; before it the sample's middle event, between the classify launch and the
+    // group-by (last call of the sample only; launches without a group-by have none)
+    const bool mid = c->t_left == 1 && p.gb;
     if (mid) HIP_TRY(hipEventRecord(c->ev[c->ev_used + 1], s));
-    if (group_by) {
-        // bins for up to kHistRange rules per workgroup; packet chunks halved (down to
-        // kHistChunkMin) while the grid has fewer than about kHistTarget workgroups
-        // (over the rules that can match, sorted indexes 0..nrules-1: the padding block never
-        // does, and counting it cost config D a fifth range pass over the batch)
-        const uint32_t nrules = c->nrules ? c->nrules : 1u;
-        const uint32_t range = nrules < kHistRange ? nrules : kHistRange;
-        const uint32_t nr = (nrules + range - 1) / range;
-        uint32_t chunk = kHistChunk;
-        while (chunk > kHistChunkMin && ((n + chunk / 2 - 1) / (chunk / 2)) * nr <= kHistTarget)
-            chunk >>= 1;
-        const dim3 hg((uint32_t)((n + chunk - 1) / chunk), nr);
-        // dense partials: one 8-byte bin per chunk and rule, summed by upe_hist_reduce
-        const size_t part_words = (size_t)hg.x * nrules;
-        if (part_words > c->hist_part_alloc) {
-            if (c->hist_part) (void)hipFree(c->hist_part);
-            c->hist_part = nullptr;
-            c->hist_part_alloc = 0;
-            HIP_TRY(hipMalloc(&c->hist_part, part_words * sizeof(unsigned long long)));
-            c->hist_part_alloc = part_words;
-        }
-        static std::atomic<uint64_t> hist_attr{0};   // 128 KB of dynamic LDS, once per device
-        if (!(hist_attr.fetch_or(1ull << (c->device & 63)) & (1ull << (c->device & 63)))) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&upe_rule_hist<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)(kHistRange * sizeof(unsigned long long)));
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&upe_rule_hist<false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)(kHistRange * sizeof(unsigned long long)));
-        }
-        if (a.gb_packed)
-            hipLaunchKernelGGL(upe_rule_hist<true>, hg, dim3(kHistBlock), range * sizeof(unsigned long long), s,
-                               d_verdict, c->gb, (uint32_t)n, nrules, c->hist_part, chunk, range);
-        else
-            hipLaunchKernelGGL(upe_rule_hist<false>, hg, dim3(kHistBlock), range * sizeof(unsigned long long), s,
-                               d_verdict, c->gb, (uint32_t)n, nrules, c->hist_part, chunk, range);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(upe_hist_reduce, dim3((nrules + 255) / 256, kStatReps),
-                           dim3(256), 0, s, c->hist_part, hg.x, nrules, c->nrules_pad, c->stats_idx);
-        HIP_TRY(hipGetLastError());
-    }
-    if (c->t_left && --c->t_left == 0) {
-        HIP_TRY(hipEventRecord(c->ev[c->ev_used + 2], s));
-        c->ev_mid.push_back(mid);
-        c->ev_used += 3;
-        c->timing_launches += c->timing_span;
-    }
+    if (p.gb && launch_group_by(c, q.verdict, n, p.gb_packed != 0, s) != 0) return -1;
+    // 9., 10.
+    if (close_sample(c, s, mid) != 0) return -1;
     ++c->k;
     c->last_n = (uint32_t)n;
     c->have_batch = true;
@@ -3711,26 +3603,33 @@ extern "C" {
 
 int upe_gpu_process(upe_gpu_ctx_t* c, uint8_t* d_frames, const uint64_t* d_desc,
                     uint32_t* d_verdict, size_t n, void* stream) {
-    return process_impl(c, d_frames, d_desc, d_verdict, nullptr, nullptr, n, stream);
+    return process_impl(c, ProcessReq{d_frames, d_desc, d_verdict, n, stream});
 }
 
 int upe_gpu_process_rss(upe_gpu_ctx_t* c, uint8_t* d_frames, const uint64_t* d_desc,
                         uint32_t* d_verdict, uint32_t* d_flow_hash, size_t n, void* stream) {
-    return process_impl(c, d_frames, d_desc, d_verdict, d_flow_hash, nullptr, n, stream);
+    ProcessReq q{d_frames, d_desc, d_verdict, n, stream};
+    q.flow_hash = d_flow_hash;
+    return process_impl(c, q);
 }
 
 int upe_gpu_process_emit(upe_gpu_ctx_t* c, uint8_t* d_frames, const uint64_t* d_desc,
                          uint32_t* d_verdict, upe_hdr_rec_t* d_hdr, size_t n, void* stream) {
     if (n && !d_hdr) return fail("null header records");
-    return process_impl(c, d_frames, d_desc, d_verdict, nullptr, d_hdr, n, stream);
+    ProcessReq q{d_frames, d_desc, d_verdict, n, stream};
+    q.hdr = d_hdr;
+    return process_impl(c, q);
 }
 
 int upe_gpu_process_emit_tx(upe_gpu_ctx_t* c, uint8_t* d_frames, const uint64_t* d_desc,
                             uint32_t* d_verdict, upe_hdr_rec_t* d_hdr, uint32_t* d_tx,
                             uint32_t* d_tx_count, size_t n, void* stream) {
     if (n && (!d_hdr || !d_tx || !d_tx_count)) return fail("null header records or egress list");
-    return process_impl(c, d_frames, d_desc, d_verdict, nullptr, d_hdr, n, stream, nullptr, false,
-                        d_tx, d_tx_count);
+    ProcessReq q{d_frames, d_desc, d_verdict, n, stream};
+    q.hdr = d_hdr;
+    q.tx = d_tx;
+    q.tx_cnt = d_tx_count;
+    return process_impl(c, q);
 }
 
 int upe_gpu_process_ring_emit(upe_gpu_ctx_t* c, uint8_t* d_frames, const uint64_t* d_desc,
@@ -3742,7 +3641,10 @@ int upe_gpu_process_ring_emit(upe_gpu_ctx_t* c, uint8_t* d_frames, const uint64_
     if (n % 1024 != 0) return fail("a ring batch must hold a multiple of 1024 packets");
     if (n * count > kMaxLaunch) return fail("a ring holds at most 2^24 packets");
     const RingReq r{n, reinterpret_cast<unsigned long long*>(d_done_ns)};
-    return process_impl(c, d_frames, d_desc, d_verdict, nullptr, d_hdr, n * count, stream, &r);
+    ProcessReq q{d_frames, d_desc, d_verdict, n * count, stream};
+    q.hdr = d_hdr;
+    q.ring = &r;
+    return process_impl(c, q);
 }
 
 }  // extern "C"
@@ -3890,26 +3792,16 @@ int host_roundtrip(upe_gpu_ctx_t* c, uint8_t* h_frames, size_t frames_bytes,
         if (sl.busy) HIP_TRY(hipEventSynchronize(sl.out_done));   // the slot's last D2H is done
         sl.busy = false;
         const size_t span = (size_t)(hi - lo);
-        if (span > sl.frames_cap) {
-            if (sl.frames) HIP_TRY(hipFree(sl.frames));
-            sl.frames = nullptr;
-            sl.frames_cap = 0;
-            const size_t want = span + span / 4;
-            HIP_TRY(hipMalloc(&sl.frames, want));
-            sl.frames_cap = want;
-        }
-        if (m > sl.pk_cap || (emit && !sl.hdr)) {
-            for (void* b : {(void*)sl.desc, (void*)sl.verdict, (void*)sl.hdr})
-                if (b) HIP_TRY(hipFree(b));
-            sl.desc = nullptr;
-            sl.verdict = nullptr;
-            sl.hdr = nullptr;
-            const size_t cap = std::max(m, sl.pk_cap);
-            sl.pk_cap = 0;
-            HIP_TRY(hipMalloc(&sl.desc, cap * sizeof(uint64_t)));
-            HIP_TRY(hipMalloc(&sl.verdict, cap * sizeof(uint32_t)));
-            if (emit) HIP_TRY(hipMalloc(&sl.hdr, cap * sizeof(upe_hdr_rec_t)));
-            sl.pk_cap = cap;
+        if (sl.frames.reserve(span, span + span / 4) != 0) return -1;
+        // (verdict, made after desc, holds the slot's packet capacity)
+        if (m > sl.verdict.cap || (emit && !sl.hdr)) {
+            const size_t cap = std::max(m, sl.verdict.cap);
+            sl.desc.reset();
+            sl.verdict.reset();
+            sl.hdr.reset();
+            if (sl.desc.reserve(cap, cap) != 0 || sl.verdict.reserve(cap, cap) != 0 ||
+                (emit && sl.hdr.reserve(cap, cap) != 0))
+                return -1;
         }
         // In place: a chunk whose bytes interleave with an earlier chunk's (descriptors in any
         // order, e.g. pool addresses) must read them only after that chunk's copy-back has
@@ -3927,11 +3819,12 @@ int host_roundtrip(upe_gpu_ctx_t* c, uint8_t* h_frames, size_t frames_bytes,
         HIP_TRY(hipStreamWaitEvent(c->stream, sl.in_done, 0));
         // the descriptors keep their offsets relative to h_frames: hand the kernel a base that
         // maps offset lo onto the slot (lo is a multiple of 16, so the base stays aligned)
-        uint8_t* base = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(sl.frames) - lo);
+        uint8_t* base = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(sl.frames.p) - lo);
         // (the host-path kernel instantiation: profiles keep these launches apart)
-        if (process_impl(c, base, sl.desc, sl.verdict, nullptr, emit ? sl.hdr : nullptr, m,
-                         nullptr, nullptr, true) != 0)
-            return -1;
+        ProcessReq q{base, sl.desc, sl.verdict, m, nullptr};
+        q.hdr = emit ? sl.hdr.p : nullptr;
+        q.host = true;
+        if (process_impl(c, q) != 0) return -1;
         HIP_TRY(hipEventRecord(sl.k_done, c->stream));
         if (issue_back(s, e, si, lo, wb) != 0) return -1;
         if (emit) pending.push_back(Done{s, e, si, lo});
@@ -4016,7 +3909,9 @@ int upe_gpu_process_mapped(upe_gpu_ctx_t* c, uint8_t* h_frames, const uint64_t* 
     const uint64_t* d = f ? mapped(h_desc, "h_desc") : nullptr;
     uint32_t* v = d ? mapped(h_verdict, "h_verdict") : nullptr;
     if (!v) return -1;
-    return process_impl(c, f, d, v, nullptr, nullptr, n, stream, nullptr, true);
+    ProcessReq q{f, d, v, n, stream};
+    q.host = true;
+    return process_impl(c, q);
 }
 
 int upe_gpu_process_mapped_emit(upe_gpu_ctx_t* c, uint8_t* h_frames, const uint64_t* h_desc,
@@ -4031,7 +3926,10 @@ int upe_gpu_process_mapped_emit(upe_gpu_ctx_t* c, uint8_t* h_frames, const uint6
     uint32_t* v = d ? mapped(h_verdict, "h_verdict") : nullptr;
     upe_hdr_rec_t* h = v ? mapped(h_hdr, "h_hdr") : nullptr;
     if (!h) return -1;
-    return process_impl(c, f, d, v, nullptr, h, n, stream, nullptr, true);
+    ProcessReq q{f, d, v, n, stream};
+    q.hdr = h;
+    q.host = true;
+    return process_impl(c, q);
 }
 
 int upe_gpu_process_batches(upe_gpu_ctx_t* c, uint8_t* const* d_frames_list, const uint64_t* d_desc,
@@ -4051,10 +3949,11 @@ int upe_gpu_process_queue_emit(upe_gpu_ctx_t* c, const upe_gpu_batch_t* batches,
     // on MI355X: DESIGN.md §8, round 3); every batch is checked before any is queued
     for (size_t k = 0; k < count; ++k)
         if (batches[k].n && !batches[k].hdr) return fail("null header records in a queued batch");
-    for (size_t k = 0; k < count; ++k)
-        if (process_impl(c, batches[k].frames, batches[k].desc, batches[k].verdict, nullptr,
-                         batches[k].hdr, batches[k].n, stream) != 0)
-            return -1;
+    for (size_t k = 0; k < count; ++k) {
+        ProcessReq q{batches[k].frames, batches[k].desc, batches[k].verdict, batches[k].n, stream};
+        q.hdr = batches[k].hdr;
+        if (process_impl(c, q) != 0) return -1;
+    }
     return 0;
 }
 
@@ -4088,13 +3987,7 @@ int upe_gpu_compact(upe_gpu_ctx_t* c, const uint32_t* d_verdict, size_t n, uint3
         return 0;
     }
     const uint32_t nb = (uint32_t)((n + kCompactBlock - 1) / kCompactBlock);
-    if (nb > c->compact_alloc) {
-        if (c->compact_counts) HIP_TRY(hipFree(c->compact_counts));
-        c->compact_counts = nullptr;
-        c->compact_alloc = 0;
-        HIP_TRY(hipMalloc(&c->compact_counts, nb * sizeof(uint32_t)));
-        c->compact_alloc = nb;
-    }
+    if (c->compact_counts.reserve(nb, nb) != 0) return -1;
     hipLaunchKernelGGL(upe_compact_count, dim3(nb), dim3(256), 0, s, d_verdict, (uint32_t)n, code,
                        c->compact_counts);
     HIP_TRY(hipGetLastError());
@@ -4125,15 +4018,10 @@ static int rx_dispatch(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t
         return 0;
     }
     const size_t need = upe_rx_scratch_bytes((uint32_t)n, rings);
-    if (need > c->rx_alloc) {
-        if (c->rx_scratch) HIP_TRY(hipFree(c->rx_scratch));
-        c->rx_scratch = nullptr;
-        c->rx_alloc = 0;
-        HIP_TRY(hipMalloc(&c->rx_scratch, need + need / 4));
-        c->rx_alloc = need + need / 4;
-    }
+    if (c->rx_scratch.reserve(need, need + need / 4) != 0) return -1;
     HIP_TRY(upe_rx_launch(d_frames, d_desc, (uint32_t)n, rings, rr_start & (rings - 1), d_ring,
-                          d_flow_hash, d_index, d_desc_out, d_counts, c->rx_scratch, s, ev));
+                          d_flow_hash, d_index, d_desc_out, d_counts,
+                          reinterpret_cast<uint32_t*>(c->rx_scratch.p), s, ev));
     return 0;
 }
 
@@ -4152,20 +4040,15 @@ int upe_gpu_rx_dispatch_timed(upe_gpu_ctx_t* c, const uint8_t* d_frames, const u
                               uint64_t* d_counts, void* stream, float* ms) {
     if (!c || !ms || n == 0) return fail("null context, no output or an empty batch");
     DEV_SCOPE(c->device);
-    hipEvent_t ev[4] = {};
-    int rc = 0;
-    for (auto& e : ev)
-        if (hipEventCreate(&e) != hipSuccess) rc = fail("hipEventCreate");
-    if (rc == 0)
-        rc = rx_dispatch(c, d_frames, d_desc, n, rings, rr_start, d_ring, d_flow_hash, d_index,
-                         d_desc_out, d_counts, stream, ev);
-    if (rc == 0 && hipEventSynchronize(ev[3]) != hipSuccess) rc = fail("hipEventSynchronize");
-    for (int k = 0; k < 3 && rc == 0; ++k)
-        if (hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]) != hipSuccess)
-            rc = fail("hipEventElapsedTime");
-    for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
-    return rc;
+    Events<4> ev;
+    if (ev.create() != 0 ||
+        rx_dispatch(c, d_frames, d_desc, n, rings, rr_start, d_ring, d_flow_hash, d_index,
+                    d_desc_out, d_counts, stream, ev.e) != 0)
+        return -1;
+    HIP_TRY(hipEventSynchronize(ev.e[3]));
+    for (int k = 0; k < 3; ++k)
+        if (ev.elapsed(&ms[k], k, k + 1) != 0) return -1;
+    return 0;
 }
 
 // The egress batch builder (reference src/worker.c:240-243, 287-303: the frames queued for
@@ -4203,15 +4086,9 @@ static int egress_pack(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t
     if (out < fr_end && fr < out + (out_bytes ? out_bytes : 1))
         return fail("d_out overlaps d_frames");
     const size_t need = upe_egress_scratch_bytes((uint32_t)n);
-    if (need > c->eg_alloc) {
-        if (c->eg_scratch) HIP_TRY(hipFree(c->eg_scratch));
-        c->eg_scratch = nullptr;
-        c->eg_alloc = 0;
-        HIP_TRY(hipMalloc(&c->eg_scratch, need + need / 4));
-        c->eg_alloc = need + need / 4;
-    }
+    if (c->eg_scratch.reserve(need, need + need / 4) != 0) return -1;
     HIP_TRY(upe_egress_launch(d_frames, d_desc, d_verdict, d_hdr, (uint32_t)n, d_out, out_bytes,
-                              d_out_desc, d_out_index, d_info, c->eg_scratch, s, ev));
+                              d_out_desc, d_out_index, d_info, c->eg_scratch.p, s, ev));
     return 0;
 }
 
@@ -4236,32 +4113,22 @@ int upe_gpu_egress_pack_timed(upe_gpu_ctx_t* c, const uint8_t* d_frames, const u
         return fail("null context, no output or an empty batch");
     DEV_SCOPE(c->device);
     hipStream_t s = pick(c, stream);
-    hipEvent_t ev[6] = {};
-    int rc = 0;
-    for (auto& e : ev)
-        if (hipEventCreate(&e) != hipSuccess) rc = fail("hipEventCreate");
-    if (rc == 0)
-        rc = egress_pack(c, d_frames, d_desc, d_verdict, d_hdr, n, d_out, out_bytes, d_out_desc,
-                         d_out_index, d_info, stream, ev);
+    Events<6> ev;
+    if (ev.create() != 0 ||
+        egress_pack(c, d_frames, d_desc, d_verdict, d_hdr, n, d_out, out_bytes, d_out_desc,
+                    d_out_index, d_info, stream, ev.e) != 0)
+        return -1;
     upe_egress_info_t info = {};
-    if (rc == 0 && (hipMemcpyAsync(&info, d_info, sizeof(info), hipMemcpyDeviceToHost, s) !=
-                        hipSuccess ||
-                    hipStreamSynchronize(s) != hipSuccess))
-        rc = fail("reading the pack's info");
-    if (rc == 0 && (hipEventRecord(ev[4], s) != hipSuccess ||
-                    hipMemcpyAsync(d_copy, d_out, info.bytes, hipMemcpyDeviceToDevice, s) !=
-                        hipSuccess ||
-                    hipEventRecord(ev[5], s) != hipSuccess ||
-                    hipEventSynchronize(ev[5]) != hipSuccess))
-        rc = fail("the device-to-device copy");
-    for (int k = 0; k < 3 && rc == 0; ++k)
-        if (hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]) != hipSuccess)
-            rc = fail("hipEventElapsedTime");
-    if (rc == 0 && hipEventElapsedTime(&ms[3], ev[4], ev[5]) != hipSuccess)
-        rc = fail("hipEventElapsedTime");
-    for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
-    return rc;
+    if (hipMemcpyAsync(&info, d_info, sizeof(info), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return fail("reading the pack's info");
+    if (hipEventRecord(ev.e[4], s) != hipSuccess ||
+        hipMemcpyAsync(d_copy, d_out, info.bytes, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipEventRecord(ev.e[5], s) != hipSuccess || hipEventSynchronize(ev.e[5]) != hipSuccess)
+        return fail("the device-to-device copy");
+    for (int k = 0; k < 3; ++k)
+        if (ev.elapsed(&ms[k], k, k + 1) != 0) return -1;
+    return ev.elapsed(&ms[3], 4, 5);
 }
 
 }  // extern "C"
@@ -4327,15 +4194,12 @@ int upe_gpu_process_segmented(upe_gpu_ctx_t* c, uint8_t* d_frames, const uint64_
     DEV_SCOPE(c->device);
     hipStream_t s = pick(c, stream);
     // 1. mark and list the table-writing control packets, in packet order
-    if (n > c->ctrl_alloc) {
-        for (void* b : {(void*)c->ctrl_marks, (void*)c->ctrl_index})
-            if (b) HIP_TRY(hipFree(b));
-        c->ctrl_marks = c->ctrl_index = nullptr;
-        c->ctrl_alloc = 0;
-        HIP_TRY(hipMalloc(&c->ctrl_marks, n * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&c->ctrl_index, n * sizeof(uint32_t)));
-        if (!c->ctrl_count) HIP_TRY(hipMalloc(&c->ctrl_count, sizeof(uint64_t)));
-        c->ctrl_alloc = n;
+    if (n > c->ctrl_index.cap) {   // (the last one made: all are there when it is)
+        c->ctrl_marks.reset();
+        c->ctrl_index.reset();
+        if (c->ctrl_count.reserve(1, 1) != 0 ||   // once
+            c->ctrl_marks.reserve(n, n) != 0 || c->ctrl_index.reserve(n, n) != 0)
+            return -1;
     }
     hipLaunchKernelGGL(upe_ctrl_mark, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s,
                        d_frames, d_desc, (uint32_t)n, c->ctrl_marks);
@@ -4346,15 +4210,12 @@ int upe_gpu_process_segmented(upe_gpu_ctx_t* c, uint8_t* d_frames, const uint64_
     HIP_TRY(hipStreamSynchronize(s));
     if (cnt == 0) return upe_gpu_process(c, d_frames, d_desc, d_verdict, n, stream);
     // 2. their bytes, gathered before any segment runs (the ARP reply is built in place)
-    if (cnt > c->ctrl_win_alloc) {
-        for (void* b : {(void*)c->ctrl_win, (void*)c->ctrl_lens})
-            if (b) HIP_TRY(hipFree(b));
-        c->ctrl_win = nullptr;
-        c->ctrl_lens = nullptr;
-        c->ctrl_win_alloc = 0;
-        HIP_TRY(hipMalloc(&c->ctrl_win, cnt * kCtrlWin));
-        HIP_TRY(hipMalloc(&c->ctrl_lens, cnt * sizeof(uint32_t)));
-        c->ctrl_win_alloc = cnt;
+    if (cnt > c->ctrl_lens.cap) {   // (the last one made)
+        c->ctrl_win.reset();
+        c->ctrl_lens.reset();
+        if (c->ctrl_win.reserve(cnt * kCtrlWin, cnt * kCtrlWin) != 0 ||
+            c->ctrl_lens.reserve(cnt, cnt) != 0)
+            return -1;
     }
     hipLaunchKernelGGL(upe_ctrl_gather, dim3((uint32_t)cnt), dim3(kCtrlWin), 0, s, d_frames,
                        d_desc, c->ctrl_index, c->ctrl_win, c->ctrl_lens);
@@ -4525,8 +4386,7 @@ int upe_gpu_reset_stats(upe_gpu_ctx_t* c) {
     HIP_TRY(hipMemsetAsync(&c->st->acc_stats[0][0], 0, sizeof(c->st->acc_stats), c->stream));
     HIP_TRY(hipMemsetAsync(c->stats, 0, c->cap * 2 * sizeof(unsigned long long), c->stream));
     if (c->stats_idx)
-        HIP_TRY(hipMemsetAsync(c->stats_idx, 0,
-                               (size_t)c->rules_alloc * 2 * kStatReps * sizeof(unsigned long long),
+        HIP_TRY(hipMemsetAsync(c->stats_idx, 0, c->stats_idx.cap * sizeof(unsigned long long),
                                c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_batch = false;
