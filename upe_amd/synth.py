@@ -1023,7 +1023,8 @@ def config_edge(repeat: int = 4, seed: int = 5) -> Workload:
     for i, (f, _) in enumerate(frames_b):
         b = np.frombuffer(f[:128], np.uint8)
         h[i, : len(b)] = b
-    # store the whole frame bytes (not just `len`): bytes past len must be ignored
+    # pack_frames stores only the first `len` bytes of each row: the bytes past len are zero here
+    # (tests/gates.py builds the batches whose tails are not)
     frames, desc = pack_frames(h, np.maximum(lens, 0))
     arp = arp_table(16, [(0x0A800005, bytes.fromhex("aabbccdd0005")),
                          (0x0A800015, bytes.fromhex("aabbccdd0015")),   # same slot as .5
