@@ -259,7 +259,11 @@ int upe_rules_match_host(const upe_rule_t *rules, size_t count, const upe_flow_k
 
 /* Upload a snapshot of the neighbour tables' slot arrays (arpt->entries / ndpt->entries with
  * their power-of-two capacities).  Lookups probe exactly as arp_get_mac/ndp_get_mac do.
- * Either table may be NULL with capacity 0 (every lookup misses). */
+ * Either table may be NULL with capacity 0 (every lookup misses).  All or nothing: the new
+ * snapshot is built and uploaded beside the previous one and swapped in once it is whole, so a
+ * call that fails (-1: an allocation, a copy, the index placement) keeps the previous snapshot
+ * and the context goes on classifying with it.  The price is a peak of old plus new index on the
+ * device during the call, 16 bytes per ARP index slot and 32 per NDP index slot. */
 int upe_gpu_load_neigh(upe_gpu_ctx_t *ctx, const upe_arp_entry_t *arp, size_t arp_capacity,
                        const upe_ndp_entry_t *ndp, size_t ndp_capacity);
 

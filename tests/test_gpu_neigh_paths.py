@@ -4,7 +4,8 @@ in LDS and looked up there; larger ones are read from memory (upe_gpu.hip `a.arp
 NDP table of a config-C stream (IMIX, v4 + v6, 1k rules) past 2048 slots — extra reachable
 entries that no packet is aimed at — and compare every output with the oracle: one table in
 memory and the other in LDS, both in memory, and with a starting L1 state that disagrees with
-the table (the look-back path), in both output modes."""
+the table (the look-back path), in both output modes.  One context also takes four snapshots in a
+row (none, one entry per family, in memory, none), a 256-packet batch under each."""
 from __future__ import annotations
 
 import dataclasses
@@ -69,6 +70,52 @@ def _check(worker_factory, wl, emit, l1=None, what=""):
 def test_neighbour_index_in_memory(gpu_worker_factory, arp_extra, ndp_extra, emit):
     wl = _grow(synth.config_c(n=120_000, seed=81), arp_extra, ndp_extra, 81)
     _check(gpu_worker_factory, wl, emit, what=f"arp+{arp_extra} ndp+{ndp_extra} emit={emit}")
+
+
+@pytest.fixture(scope="module")
+def reload_steps():
+    """One 256-packet batch (config C with IPv6 forwarded, so both families look up) under four
+    snapshots in a row, and the oracle's outputs of each step continued from the step before:
+    no tables, one-slot tables holding the first packet's destination of each family, tables whose
+    indexes pass 2048 slots (read from memory), no tables again."""
+    wl = synth.config_c(n=256, seed=83, v6_forwarding=True)
+    offs = wl.desc >> np.uint64(16)
+    fr = wl.frames
+    o4 = int(next(o for o in offs if fr[o + 12] == 0x08 and fr[o + 13] == 0x00))
+    o6 = int(next(o for o in offs if fr[o + 12] == 0x86 and fr[o + 13] == 0xDD))
+    none = dataclasses.replace(wl, arp=wl.arp[:0], ndp=wl.ndp[:0])
+    one = dataclasses.replace(
+        wl, arp=synth.arp_table(1, [(int.from_bytes(bytes(fr[o4 + 30:o4 + 34]), "big"),
+                                     bytes.fromhex("02aa00000004"))]),
+        ndp=synth.ndp_table(1, [(bytes(fr[o6 + 38:o6 + 54]), bytes.fromhex("02aa00000006"))]))
+    steps, prev = [], None
+    for s in (none, one, _grow(wl, 1500, 1500, 83), none):
+        prev = oracle.run_restated(s, l1=prev and prev.l1, counters=prev and prev.counters,
+                                   rule_stats=prev and prev.rule_stats)
+        steps.append((s, prev))
+    return steps
+
+
+@pytest.mark.parametrize("emit", [False, True])
+def test_neighbour_reloads_on_one_context(gpu_worker_factory, reload_steps, emit):
+    """upe_gpu_load_neigh again and again on one context: every snapshot replaces the one before
+    it whole (the second step's entries are gone in the third's tables and the last has none), the
+    L1 entries, counters and rule_stats carry on."""
+    w = gpu_worker_factory(reload_steps[0][0].capacity)
+    try:
+        w.configure(reload_steps[0][0])
+        for i, (wl, r) in enumerate(reload_steps):
+            what = f"step {i} emit={emit}"
+            w.load_neigh(wl.arp, wl.ndp)
+            frames, verdict, counters, stats, l1 = gpu.run_workload(wl, worker=w, emit=emit)
+            bad = np.nonzero(verdict != r.verdict)[0]
+            assert bad.size == 0, f"{what}: {bad.size} verdicts differ, first {bad[:8].tolist()}"
+            assert np.array_equal(frames, r.frames), f"{what}: frames differ"
+            assert counters.tobytes() == np.asarray(r.counters).tobytes(), what
+            assert np.array_equal(stats, r.rule_stats), what
+            assert l1.tobytes() == np.asarray(r.l1).tobytes(), what
+    finally:
+        w.close()
 
 
 @pytest.mark.parametrize("emit", [False, True])

@@ -1,9 +1,12 @@
 """Wall time of upe_gpu_load_rules (rule compile + index build + upload) for the large-table
-cases (the decision tree is built on the worker thread at a reload).
+cases (the decision tree is built on the worker thread at a reload), and of the two
+other calls that swap what a context classifies with: upe_gpu_reload_rules (the same table, a
+fresh rule_stats) and upe_gpu_load_neigh (the case's own ARP and NDP slot arrays).
 
   python tools/load_time.py [cases...]     cases: C3 CF C6 F16k M64k D (default all)
 
-Median of 3 loads each, on GPU 0; prints one JSON line per case with the index kind chosen."""
+Median of 3 loads each (of 9 neighbour loads), on GPU 0; prints one JSON line per case with the
+index kind chosen."""
 from __future__ import annotations
 
 import json
@@ -39,9 +42,21 @@ def main() -> None:
             t0 = time.perf_counter()
             w.load_rules(rs)
             ts.append(time.perf_counter() - t0)
+        def timed(fn, reps):
+            out = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                fn()
+                out.append(time.perf_counter() - t0)
+            return round(1e3 * statistics.median(out), 3)
+
+        reload_ms = timed(lambda: w.reload_rules(rs, wl.capacity, want_old=False), 3)
+        w.load_neigh(wl.arp, wl.ndp)   # warm-up
+        neigh_ms = timed(lambda: w.load_neigh(wl.arp, wl.ndp), 9)
         kind = w.rule_index_kind()
         w.close()
         print(json.dumps({"case": c, "rules": int(len(rs)), "load_ms": round(1e3 * statistics.median(ts), 2),
+                          "reload_ms": reload_ms, "neigh_ms": neigh_ms,
                           "index": {0: "linear scan", 1: "tuple space", 2: "decision tree"}.get(kind, kind)}),
               flush=True)
 

@@ -146,6 +146,12 @@ UPE_HD UPE_INLINE uint32_t slot3(uint32_t k, uint32_t seed, uint32_t bits) {
     const uint32_t x = (k ^ (seed * 0x9E3779B9u)) * 0x27D4EB2Fu;
     return ((x ^ (x >> 15)) * 0x165667B1u) >> (32 - bits);
 }
+// The NDP index's 32-bit key: the fold of an address's four LE words (different addresses may
+// share it; a slot hits on the full address).
+UPE_HD UPE_INLINE uint32_t fold_v6(const uint32_t ip[4]) {
+    return (ip[0] * 0x9E3779B1u) ^ (ip[1] * 0x85EBCA77u) ^ (ip[2] * 0xC2B2AE3Du) ^
+           (ip[3] * 0x27D4EB2Fu);
+}
 // Key hash of the tuple-space index (host and device agree bit for bit).
 UPE_HD UPE_INLINE uint32_t tss_hash(const uint32_t* k, int nw, uint32_t seed) {
     uint32_t h = seed ^ 0x9E3779B9u;

@@ -370,11 +370,7 @@ __device__ __forceinline__ void store16(uint4* p, uint4 v) { *p = v; }
 // device batches (C +12 us, B +6.5 us per 1M) and for host-memory batches (config B mapped 537
 // vs 666-680 Mpps in place, C 214 vs 319; profiles/r03/v5_host_nt_ab.txt).
 
-// ---- neighbour lookups ----------------------------------------------------------------------
-__host__ __device__ __forceinline__ uint32_t fold_v6(const uint32_t ip[4]) {
-    return (ip[0] * 0x9E3779B1u) ^ (ip[1] * 0x85EBCA77u) ^ (ip[2] * 0xC2B2AE3Du) ^
-           (ip[3] * 0x27D4EB2Fu);
-}
+// ---- neighbour lookups (fold_v6: upe_dev.h) -------------------------------------------------
 __device__ __forceinline__ bool arp_slot_hit(const uint4& e, uint32_t ip) {
     return ((e.z >> 16) & 1u) && e.x == ip;
 }
@@ -2362,6 +2358,85 @@ struct Events {
     }
 };
 
+// The neighbour snapshot on the device (NeighIndex): one value, uploaded whole and then swapped
+// into the context (upe_gpu_load_neigh).
+struct NeighTable {
+    DevBuf<uint4> arp, ndp;
+    uint32_t arp_bits = 0, arp_seed = 0, ndp_bits = 0, ndp_seed = 0;
+    // (an empty table)
+    int upload(const NeighImage& im) {
+        if (arp.put(im.arp.data(), im.arp.size()) || ndp.put(im.ndp.data(), im.ndp.size()))
+            return -1;
+        arp_bits = im.arp_bits, arp_seed = im.arp_seed;
+        ndp_bits = im.ndp_bits, ndp_seed = im.ndp_seed;
+        return 0;
+    }
+};
+
+// The compiled rule table on the device (upe_rule_image, upe_rules.h): one value, uploaded whole
+// and then swapped into the context (install_image).
+struct DeviceTable {
+    DevBuf<RuleV4> rv4;
+    DevBuf<RuleV6> rv6;
+    DevBuf<int2> rinfo;
+    DevBuf<uint4> fam;                // FamTable image (linear-scan tables > kSmallRules)
+    uint32_t fam4 = 0, fam6 = 0, fam_all = 0, fam_x1idx = 0;
+    // whether a packet of each family can be forwarded at all under the table: some rule it can
+    // reach first (up to its family's first catch-all) forwards
+    bool fwd4 = true, fwd6 = true;
+    uint32_t nrules = 0, nrules_pad = 0;
+    std::vector<int2> rinfo_host;     // (action, rule_id) per sorted index
+    // tuple-space index of large tables (null when the linear scan is used)
+    DevBuf<TssGroup> tg4, tg6;
+    DevBuf<uint4> tt4, tt6;
+    DevBuf<uint16_t> tfs;             // staged fingerprint image
+    uint32_t nfs = 0;                 // its length in uint4
+    uint32_t ng4 = 0, ng6 = 0;
+    bool tss = false;
+    // decision-tree index over the family lists (null / tree_ok false when not used)
+    DevBuf<uint4> tree;
+    bool tree_ok = false;
+    uint32_t tree_words = 0, tree_loff = 0;
+    upe_rule_index_info_t tree_info = {};
+
+    // (an empty table) every image of `im` on the device
+    int upload(const upe_rule_image& im) {
+        const TreeImage& t = im.t;
+        if (rv4.put(im.v4.data(), im.pad) || rv6.put(im.v6.data(), im.pad) ||
+            rinfo.put(im.info.data(), im.pad) || fam.put(im.fimg.data(), im.fimg.size()) ||
+            (im.tss && (tfs.put(im.fps.data(), im.fps.size()) ||
+                        tg4.put(im.f4.groups.data(), im.f4.groups.size()) ||
+                        tg6.put(im.f6.groups.data(), im.f6.groups.size()) ||
+                        tt4.put(im.f4.slots.data(), im.f4.slots.size()) ||
+                        tt6.put(im.f6.slots.data(), im.f6.slots.size()))) ||
+            (im.tree_ok && tree.put(im.timg.data(), im.timg.size())))
+            return -1;
+        fam4 = im.fam4, fam6 = im.fam6, fam_all = im.fam_all, fam_x1idx = im.fam_x1idx;
+        fwd4 = im.fwd4, fwd6 = im.fwd6;
+        nrules = (uint32_t)im.count;
+        nrules_pad = (uint32_t)im.pad;
+        rinfo_host = im.info;
+        tss = im.tss;
+        nfs = tss ? (uint32_t)(im.fps.size() / 8) : 0u;
+        ng4 = tss ? (uint32_t)im.f4.groups.size() : 0u;
+        ng6 = tss ? (uint32_t)im.f6.groups.size() : 0u;
+        tree_ok = im.tree_ok;
+        tree_words = tree_ok ? (uint32_t)im.timg.size() : 0u;
+        tree_loff = tree_ok ? (uint32_t)(2 * t.nodes.size()) : 0u;
+        if (tree_ok)
+            tree_info = upe_rule_index_info_t{(uint64_t)t.nodes.size(), (uint64_t)t.leaves.size(),
+                                              t.depth[0], t.depth[1], t.max_leaf,
+                                              t.trees[0] | t.trees[1] << 16};
+        return 0;
+    }
+    // The plan's view of the loaded tables (upe_plan.h): this one's, the neighbour indexes' sizes
+    // and whether a tree may be staged in LDS (a context option).
+    TableShape shape(const NeighTable& nb, bool tree_stage) const {
+        return TableShape{tss, nrules, nrules_pad, nb.arp_bits, nb.ndp_bits, nfs,
+                          tree_ok, tree_stage, tree_words, fam4, fam6, fam_all != 0};
+    }
+};
+
 // ------------------------------------------------------------------------------------------
 // Control packets that write a neighbour table (upe_gpu_process_segmented).  A packet is
 // marked when handle_control_packet (reference src/worker.c:23-104) may call arp_update or
@@ -2465,87 +2540,66 @@ struct ApplyPool {
 struct upe_gpu_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    size_t cap = 0;                // rule_stats capacity
-    // rules
-    DevBuf<RuleV4> rv4;
-    DevBuf<RuleV6> rv6;
-    DevBuf<int2> rinfo;
-    DevBuf<uint4> fam;                         // FamTable image (linear-scan tables > kSmallRules)
-    uint32_t fam4 = 0, fam6 = 0;
-    uint32_t fam_all = 0;
-    // whether a packet of each family can be forwarded at all under the current table: some
-    // rule it can reach first (up to its family's first catch-all) forwards
-    bool fwd4 = true, fwd6 = true;
-    uint32_t fam_x1idx = 0;
-    // decision-tree index over the family lists (null / tree_ok false when not used)
-    DevBuf<uint4> tree;
-    uint32_t tree_words = 0, tree_loff = 0;
-    bool tree_ok = false;
-    bool tree_stage = true;                    // stage the image in LDS when it fits
-    upe_rule_index_info_t tree_info = {};
-    uint32_t nrules = 0, nrules_pad = 0;
-    DevBuf<unsigned long long> stats_idx;      // [kStatReps][pad][2] totals per sorted index, pad
-                                               // the largest table so far
+    int cus = 256;
+    int blocks_per_cu_override = 0;   // UPE_GPU_BLOCKS_PER_CU (diagnostic)
     bool host_tag = false;   // launches on behalf of a host-side loop (upe_gpu_tag_host)
-    DevBuf<unsigned long long> hist_part;      // [chunks][nrules] dense group-by partials
-    DevBuf<uint32_t> gb;                       // group-by keys (u32), or u16 lengths
-    std::vector<int2> rinfo_host;              // (action, rule_id) per sorted index
-    // tuple-space index of large tables (null when the linear scan is used)
-    DevBuf<TssGroup> tg4, tg6;
-    DevBuf<uint4> tt4, tt6;
-    DevBuf<uint16_t> tfs;             // staged fingerprint image
-    uint32_t nfs = 0;                 // its length in uint4
-    uint32_t ng4 = 0, ng6 = 0;
-    bool tss = false;
-    DevBuf<uint32_t> compact_counts;      // upe_gpu_compact: per-block counts
-    DevBuf<uint8_t> rx_scratch;           // upe_gpu_rx_dispatch: the passes' tile table (upe_rx.hip)
-    DevBuf<uint8_t> eg_scratch;           // upe_gpu_egress_pack: the tile table (upe_egress.hip)
-    // upe_gpu_process_segmented scratch: marks / index per packet, gathered windows per mark
-    DevBuf<uint32_t> ctrl_marks, ctrl_index;
-    DevBuf<uint64_t> ctrl_count;
-    DevBuf<uint8_t> ctrl_win;
-    DevBuf<uint32_t> ctrl_lens;
-    // neighbour tables (reachable-entry indexes)
-    DevBuf<uint4> arp;
-    uint32_t arp_bits = 0, arp_seed = 0;
-    DevBuf<uint4> ndp;
-    uint32_t ndp_bits = 0, ndp_seed = 0;
+    bool tree_stage = true;  // stage a decision tree's image in LDS when it fits (UPE_GPU_TREE_LDS)
+    uint32_t port_mac_lo = 0, port_mac_hi = 0, port_ip4 = 0;
+    // what the launches classify with: each a value that a load uploads whole and then swaps in
+    DeviceTable table;             // the compiled rule table (install_image)
+    NeighTable neigh;              // the neighbour snapshot (upe_gpu_load_neigh)
+    // rule_stats: they outlive a table (upe_gpu_load_rules credits them by rule_id)
+    struct Stats {
+        size_t cap = 0;                       // rule_stats capacity
+        DevBuf<unsigned long long> rule;      // [cap][2] rule_stats by rule_id
+        DevBuf<unsigned long long> idx;       // [kStatReps][pad][2] totals per sorted index, pad
+                                              // the largest table so far
+        DevBuf<unsigned long long> hist_part; // [chunks][nrules] dense group-by partials
+        DevBuf<uint32_t> gb;                  // group-by keys (u32), or u16 lengths
+    } stats;
     // state: one DevState allocation (see "Sequential state between batches")
     DevBuf<DevState> st;
-    uint64_t k = 0;                // launches so far: the next batch is batch k
-    uint32_t last_n = 0;           // the last batch's size (batch_info)
-    DevBuf<unsigned long long> stats;   // [cap][2]
     DevBuf<TilePay> pay;           // [2][paycap] per-workgroup last-hit payloads, by batch parity
     uint32_t paycap = 0;           // largest grid
-    // per-batch scratch, for tiles of kWaves chunks
-    DevBuf<uint32_t> lb;           // a look-back flag per chunk (zeroed at allocation)
-    DevBuf<uint32_t> defer;        // 64 deferred look-back candidates (two words each) per chunk
-    uint32_t lb_spin = 5000;       // look-back wait before deferring (UPE_GPU_LB_SPIN, 100 MHz ticks)
-    bool lb_sync = false;          // UPE_GPU_LB_SYNC=1: wait for each launch's agreement report
-    bool allow_nolb = true;        // UPE_GPU_NOLB=0: never use the kernels without look-back
+    // launch bookkeeping
+    uint64_t k = 0;                // launches so far: the next batch is batch k
+    uint32_t last_n = 0;           // the last batch's size (batch_info)
     int last_var = -1;             // kernel variant of the last classify launch
     uint32_t last_grid = 0;
-    DevBuf<unsigned long long> ring_wg;   // ring launches: per-batch counters + time origin
+    bool have_batch = false;
     // every launch and state upload is ordered after the previous one, whatever its stream
     hipStream_t last_stream = nullptr;
     hipEvent_t order_ev = nullptr;
-    int cus = 256;
-    std::map<uint64_t, uint32_t> resident;   // persistent grid per (lds, tss, emit) (census)
-    int blocks_per_cu_override = 0;   // UPE_GPU_BLOCKS_PER_CU (diagnostic)
-    uint32_t port_mac_lo = 0, port_mac_hi = 0, port_ip4 = 0;
-    bool have_batch = false;
+    std::map<uint64_t, uint32_t> resident;   // persistent grid per (lds, variant word) (census)
+    hipEvent_t marks[4] = {};      // worker loop completion marks (upe_gpu_mark)
+    // the look-back between a batch's chunks, and the switch to the kernel without it (kNoLB): the
+    // launches' start-state agreement, written by the device into host-mapped memory, and the
+    // first launch whose report counts
+    struct LookBack {
+        // per-batch scratch, for tiles of kWaves chunks
+        DevBuf<uint32_t> flags;    // a look-back flag per chunk (zeroed at allocation)
+        DevBuf<uint32_t> defer;    // 64 deferred look-back candidates (two words each) per chunk
+        uint32_t spin = 5000;      // look-back wait before deferring (UPE_GPU_LB_SPIN, 100 MHz ticks)
+        bool sync = false;         // UPE_GPU_LB_SYNC=1: wait for each launch's agreement report
+        bool allow_nolb = true;    // UPE_GPU_NOLB=0: never use the kernels without look-back
+        bool no_lb = false;
+        uint64_t reset_k = 0;
+        unsigned long long* agree_h = nullptr;
+        unsigned long long* agree_d = nullptr;
+    } lb;
     // kernel timing (upe_gpu_timing_*)
-    bool timing = false;
-    uint32_t timing_every = 1, timing_calls = 0;   // sample every n-th process() call
-    uint32_t timing_phase = 0;     // samples open at calls c with c % timing_every == phase
-    uint32_t timing_span = 1;      // calls one sample's event pair brackets
-    uint32_t t_left = 0;           // calls left in the open sample (0: none open)
-    uint64_t timing_launches = 0;  // calls covered by closed samples
-    std::vector<hipEvent_t> ev;   // event pool, 2 per timed process() call
-    size_t ev_used = 0;            // 3 per closed sample: start, after the classify, end
-    std::vector<bool> ev_mid;      // per closed sample: the middle event was recorded
-    // host round trip (upe_gpu_process_host): copy streams and three device slots
-    hipStream_t s_in = nullptr, s_out = nullptr;
+    struct Timing {
+        bool on = false;
+        uint32_t every = 1, calls = 0;   // sample every n-th process() call
+        uint32_t phase = 0;        // samples open at calls c with c % every == phase
+        uint32_t span = 1;         // calls one sample's event pair brackets
+        uint32_t left = 0;         // calls left in the open sample (0: none open)
+        uint64_t launches = 0;     // calls covered by closed samples
+        std::vector<hipEvent_t> ev;    // event pool, 3 per sample
+        size_t ev_used = 0;        // 3 per closed sample: start, after the classify, end
+        std::vector<bool> ev_mid;  // per closed sample: the middle event was recorded
+    } timing;
+    // host round trip (upe_gpu_process_host): copy streams and the device slots
     struct HostSlot {
         DevBuf<uint8_t> frames;
         DevBuf<uint64_t> desc;          // desc, verdict (and hdr, once used) hold as many packets
@@ -2555,23 +2609,36 @@ struct upe_gpu_ctx {
         bool busy = false;
         uint64_t lo = 0, wb = 0;   // host byte range the slot's copy-back writes
     };
-    HostSlot hs[8];
-    // host threads applying emit-mode records to the caller's frames (upe_gpu_process_host_emit)
-    std::unique_ptr<struct ApplyPool> pool;
-    uint32_t host_slots = 4;       // device slots of the host round trip (UPE_GPU_HOST_SLOTS, 2..8)
-    // the kernel without look-back (kNoLB): the launches' start-state agreement, written by the
-    // device into host-mapped memory, and the first launch whose report counts
-    hipEvent_t marks[4] = {};      // worker loop completion marks (upe_gpu_mark)
-    unsigned long long* agree_h = nullptr;
-    unsigned long long* agree_d = nullptr;
-    uint64_t lb_reset_k = 0;
-    bool no_lb = false;
+    struct HostPath {
+        hipStream_t s_in = nullptr, s_out = nullptr;
+        HostSlot slots[8];
+        uint32_t nslots = 4;       // slots in use (UPE_GPU_HOST_SLOTS, 2..8)
+        // host threads applying emit-mode records to the caller's frames
+        // (upe_gpu_process_host_emit)
+        std::unique_ptr<struct ApplyPool> pool;
+    } host;
+    // upe_gpu_process_segmented scratch: marks / index per packet, gathered windows per mark
+    struct SegScratch {
+        DevBuf<uint32_t> marks, index;
+        DevBuf<uint64_t> count;
+        DevBuf<uint8_t> win;
+        DevBuf<uint32_t> lens;
+    } seg;
+    // single-use scratch
+    DevBuf<uint32_t> compact_counts;      // upe_gpu_compact: per-block counts
+    DevBuf<uint8_t> rx_scratch;           // upe_gpu_rx_dispatch: the passes' tile table (upe_rx.hip)
+    DevBuf<uint8_t> eg_scratch;           // upe_gpu_egress_pack: the tile table (upe_egress.hip)
+    DevBuf<unsigned long long> ring_wg;   // ring launches: per-batch counters + time origin
 };
 
 namespace {
 
-NeighIndex arp_index(const upe_gpu_ctx* c) { return NeighIndex{c->arp, c->arp_bits, c->arp_seed}; }
-NeighIndex ndp_index(const upe_gpu_ctx* c) { return NeighIndex{c->ndp, c->ndp_bits, c->ndp_seed}; }
+NeighIndex arp_index(const upe_gpu_ctx* c) {
+    return NeighIndex{c->neigh.arp, c->neigh.arp_bits, c->neigh.arp_seed};
+}
+NeighIndex ndp_index(const upe_gpu_ctx* c) {
+    return NeighIndex{c->neigh.ndp, c->neigh.ndp_bits, c->neigh.ndp_seed};
+}
 
 // Point the DevState at the separately allocated arrays (after any of them is reallocated).
 int publish(upe_gpu_ctx* c) {
@@ -2580,7 +2647,7 @@ int publish(upe_gpu_ctx* c) {
         uint32_t* lb;
         unsigned long long* stats;
         unsigned long long* stats_idx;
-    } p = {c->pay, c->lb, c->stats, c->stats_idx};
+    } p = {c->pay, c->lb.flags, c->stats.rule, c->stats.idx};
     static_assert(offsetof(DevState, stats_idx) - offsetof(DevState, pay) == 3 * sizeof(void*),
                   "DevState pointer block");
     HIP_TRY(hipMemcpy(reinterpret_cast<char*>(c->st.p) + offsetof(DevState, pay), &p, sizeof p,
@@ -2589,12 +2656,12 @@ int publish(upe_gpu_ctx* c) {
 }
 
 int ensure_scratch(upe_gpu_ctx* c, size_t ntiles) {
-    if (2 * 64 * ntiles * kWaves > c->defer.cap) {   // (the last one made)
-        c->lb.reset();   // both go before either comes back
-        c->defer.reset();
+    if (2 * 64 * ntiles * kWaves > c->lb.defer.cap) {   // (the last one made)
+        c->lb.flags.reset();   // both go before either comes back
+        c->lb.defer.reset();
         const size_t chunks = (ntiles + ntiles / 4 + 16) * kWaves;
-        if (c->lb.zeros(chunks) != 0 || c->defer.reserve(2 * 64 * chunks, 2 * 64 * chunks) != 0 ||
-            publish(c) != 0)
+        if (c->lb.flags.zeros(chunks) != 0 ||
+            c->lb.defer.reserve(2 * 64 * chunks, 2 * 64 * chunks) != 0 || publish(c) != 0)
             return -1;
     }
     return 0;
@@ -2619,8 +2686,8 @@ TilePay* pay_slot(upe_gpu_ctx* c, uint64_t k) { return c->pay + (size_t)(k % 2) 
 // Does the L1 state the next batch starts from agree with the tables?  (After l1_sync.)
 int refresh(upe_gpu_ctx* c) {
     if (order_on(c, c->stream) != 0) return -1;
-    c->no_lb = false;   // the entries may disagree with the new tables until a launch says not
-    c->lb_reset_k = c->k;
+    c->lb.no_lb = false;   // the entries may disagree with the new tables until a launch says not
+    c->lb.reset_k = c->k;
     hipLaunchKernelGGL(upe_refresh, dim3(1), dim3(64), 0, c->stream, l1_slot(c, c->k),
                        arp_index(c), ndp_index(c));
     HIP_TRY(hipGetLastError());
@@ -2649,8 +2716,8 @@ int arm_state(upe_gpu_ctx* c) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->k = 0;
     c->last_n = 0;
-    c->no_lb = false;
-    c->lb_reset_k = 0;
+    c->lb.no_lb = false;
+    c->lb.reset_k = 0;
     return 0;
 }
 
@@ -2873,7 +2940,7 @@ upe_gpu_ctx_t* upe_gpu_open(int device, size_t rule_capacity) {
         return nullptr;
     }
     c->device = device;
-    c->cap = rule_capacity;
+    c->stats.cap = rule_capacity;
     auto failed = [&]() {   // the message is the failed step's
         const std::string m = g_err;
         upe_gpu_close(c);
@@ -2891,7 +2958,7 @@ upe_gpu_ctx_t* upe_gpu_open(int device, size_t rule_capacity) {
         return bad(e, "hipStreamCreate");
     if ((e = hipEventCreateWithFlags(&c->order_ev, hipEventDisableTiming)) != hipSuccess)
         return bad(e, "hipEventCreate");
-    if (c->st.zeros(1) != 0 || c->stats.reserve(rule_capacity * 2, rule_capacity * 2) != 0)
+    if (c->st.zeros(1) != 0 || c->stats.rule.reserve(rule_capacity * 2, rule_capacity * 2) != 0)
         return failed();
     {
         int cus = 0;
@@ -2902,31 +2969,31 @@ upe_gpu_ctx_t* upe_gpu_open(int device, size_t rule_capacity) {
         // diagnostics: the look-back wait before deferring (0 = defer whenever a flag is not yet
         // published), a synchronous agreement report per launch (the switch to the kernel without
         // look-back then happens at a deterministic launch), no kernel without look-back
-        if (const char* v = getenv("UPE_GPU_LB_SPIN")) c->lb_spin = (uint32_t)strtoul(v, nullptr, 10);
-        if (const char* v = getenv("UPE_GPU_LB_SYNC")) c->lb_sync = v[0] == '1';
-        if (const char* v = getenv("UPE_GPU_NOLB")) c->allow_nolb = v[0] != '0';
+        if (const char* v = getenv("UPE_GPU_LB_SPIN")) c->lb.spin = (uint32_t)strtoul(v, nullptr, 10);
+        if (const char* v = getenv("UPE_GPU_LB_SYNC")) c->lb.sync = v[0] == '1';
+        if (const char* v = getenv("UPE_GPU_NOLB")) c->lb.allow_nolb = v[0] != '0';
         if (const char* v = getenv("UPE_GPU_HOST_SLOTS"))
-            c->host_slots = std::min(8u, std::max(2u, (uint32_t)strtoul(v, nullptr, 10)));
+            c->host.nslots = std::min(8u, std::max(2u, (uint32_t)strtoul(v, nullptr, 10)));
     }
     // payload slots for the largest grid a launch uses (at most 8 workgroups per CU)
     c->paycap = 8u * (uint32_t)c->cus;
     if (c->pay.zeros(2 * (size_t)c->paycap) != 0) return failed();
     // host-mapped report of each launch's start-state agreement (the kernel without look-back
     // is used once one arrives; without it, every launch keeps the look-back)
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->agree_h), sizeof(unsigned long long),
+    if (hipHostMalloc(reinterpret_cast<void**>(&c->lb.agree_h), sizeof(unsigned long long),
                       hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
-        *c->agree_h = 0;
-        if (hipHostGetDevicePointer(reinterpret_cast<void**>(&c->agree_d), c->agree_h, 0) !=
+        *c->lb.agree_h = 0;
+        if (hipHostGetDevicePointer(reinterpret_cast<void**>(&c->lb.agree_d), c->lb.agree_h, 0) !=
             hipSuccess) {
-            (void)hipHostFree(c->agree_h);
-            c->agree_h = nullptr;
-            c->agree_d = nullptr;
+            (void)hipHostFree(c->lb.agree_h);
+            c->lb.agree_h = nullptr;
+            c->lb.agree_d = nullptr;
         }
     } else {
-        c->agree_h = nullptr;
+        c->lb.agree_h = nullptr;
     }
     if (arm_state(c) != 0) return failed();
-    if ((e = hipMemsetAsync(c->stats, 0, rule_capacity * 2 * sizeof(unsigned long long),
+    if ((e = hipMemsetAsync(c->stats.rule, 0, rule_capacity * 2 * sizeof(unsigned long long),
                             c->stream)) != hipSuccess)
         return bad(e, "hipMemsetAsync");
     // An empty rule table: one padding block of never-matching rules.
@@ -2940,17 +3007,17 @@ void upe_gpu_close(upe_gpu_ctx_t* c) {
     if (!c) return;
     DevScope dg(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->timing.ev) (void)hipEventDestroy(e);
     if (c->order_ev) (void)hipEventDestroy(c->order_ev);
     for (hipEvent_t e : c->marks)
         if (e) (void)hipEventDestroy(e);
-    for (auto& sl : c->hs)
+    for (auto& sl : c->host.slots)
         for (hipEvent_t e : {sl.in_done, sl.k_done, sl.out_done})
             if (e) (void)hipEventDestroy(e);
-    if (c->s_in) (void)hipStreamSynchronize(c->s_in), (void)hipStreamDestroy(c->s_in);
-    if (c->s_out) (void)hipStreamSynchronize(c->s_out), (void)hipStreamDestroy(c->s_out);
+    if (c->host.s_in) (void)hipStreamSynchronize(c->host.s_in), (void)hipStreamDestroy(c->host.s_in);
+    if (c->host.s_out) (void)hipStreamSynchronize(c->host.s_out), (void)hipStreamDestroy(c->host.s_out);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->agree_h) (void)hipHostFree(c->agree_h);
+    if (c->lb.agree_h) (void)hipHostFree(c->lb.agree_h);
     delete c;   // the device buffers go with it (DevBuf), on the context's device
 }
 
@@ -2962,9 +3029,9 @@ namespace {
 // accumulators (acc_stats, added here), mid-size ones in kStatReps replicas (each workgroup's LDS
 // bins) and large ones too (upe_rule_hist).  The host sums the replicas and credits rule_id.
 int read_stats_idx(upe_gpu_ctx* c, std::vector<unsigned long long>& idx) {
-    const size_t E = 2 * (size_t)c->nrules_pad;
+    const size_t E = 2 * (size_t)c->table.nrules_pad;
     std::vector<unsigned long long> all(E * kStatReps);
-    HIP_TRY(hipMemcpy(all.data(), c->stats_idx, all.size() * sizeof(unsigned long long),
+    HIP_TRY(hipMemcpy(all.data(), c->stats.idx, all.size() * sizeof(unsigned long long),
                       hipMemcpyDeviceToHost));
     idx.assign(E, 0);
     for (size_t r = 0; r < (size_t)kStatReps; ++r)
@@ -2981,21 +3048,21 @@ int read_stats_idx(upe_gpu_ctx* c, std::vector<unsigned long long>& idx) {
 }
 
 int fold_stats_idx(upe_gpu_ctx* c) {
-    if (!c->stats_idx || c->rinfo_host.empty()) return 0;
-    const size_t E = 2 * (size_t)c->nrules_pad;
-    std::vector<unsigned long long> idx, st(2 * c->cap);
+    if (!c->stats.idx || c->table.rinfo_host.empty()) return 0;
+    const size_t E = 2 * (size_t)c->table.nrules_pad;
+    std::vector<unsigned long long> idx, st(2 * c->stats.cap);
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (read_stats_idx(c, idx) != 0) return -1;
     bool any = false;
     for (unsigned long long v : idx) any |= v != 0;
     if (!any) return 0;
-    HIP_TRY(hipMemcpy(st.data(), c->stats, st.size() * sizeof(unsigned long long),
+    HIP_TRY(hipMemcpy(st.data(), c->stats.rule, st.size() * sizeof(unsigned long long),
                       hipMemcpyDeviceToHost));
     for (size_t e = 0; e < E; ++e)
-        if (idx[e]) st[2 * (size_t)(uint32_t)c->rinfo_host[e >> 1].y + (e & 1)] += idx[e];
-    HIP_TRY(hipMemcpy(c->stats, st.data(), st.size() * sizeof(unsigned long long),
+        if (idx[e]) st[2 * (size_t)(uint32_t)c->table.rinfo_host[e >> 1].y + (e & 1)] += idx[e];
+    HIP_TRY(hipMemcpy(c->stats.rule, st.data(), st.size() * sizeof(unsigned long long),
                       hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(c->stats_idx, 0, E * kStatReps * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(c->stats.idx, 0, E * kStatReps * sizeof(unsigned long long)));
     HIP_TRY(hipMemset(&c->st->acc_stats[0][0], 0, sizeof(c->st->acc_stats)));
     return 0;
 }
@@ -3003,15 +3070,15 @@ int fold_stats_idx(upe_gpu_ctx* c) {
 // rule_stats[0..capacity) as the worker holds them: the per-rule_id array plus the current
 // table's per-sorted-index totals credited to their rule_id (after a device synchronisation).
 int read_rule_stats(upe_gpu_ctx* c, upe_rule_stat_t* rule_stats, size_t capacity) {
-    const size_t k = capacity < c->cap ? capacity : c->cap;
+    const size_t k = capacity < c->stats.cap ? capacity : c->stats.cap;
     memset(rule_stats, 0, capacity * sizeof(upe_rule_stat_t));
-    HIP_TRY(hipMemcpy(rule_stats, c->stats, k * sizeof(upe_rule_stat_t), hipMemcpyDeviceToHost));
-    if (c->stats_idx && !c->rinfo_host.empty()) {
-        const size_t E = 2 * (size_t)c->nrules_pad;
+    HIP_TRY(hipMemcpy(rule_stats, c->stats.rule, k * sizeof(upe_rule_stat_t), hipMemcpyDeviceToHost));
+    if (c->stats.idx && !c->table.rinfo_host.empty()) {
+        const size_t E = 2 * (size_t)c->table.nrules_pad;
         std::vector<unsigned long long> idx;
         if (read_stats_idx(c, idx) != 0) return -1;
         for (size_t e = 0; e < E; ++e) {
-            const uint32_t rid = (uint32_t)c->rinfo_host[e >> 1].y;
+            const uint32_t rid = (uint32_t)c->table.rinfo_host[e >> 1].y;
             if (!idx[e] || rid >= k) continue;
             if (e & 1) rule_stats[rid].bytes += idx[e];
             else rule_stats[rid].packets += idx[e];
@@ -3031,99 +3098,42 @@ using StatsBuf = DevBuf<unsigned long long>;
 // before the context changes: on an error the context keeps classifying with the old table and
 // its statistics.
 int install_image(upe_gpu_ctx_t* c, const upe_rule_image& im, StatsBuf* fresh, size_t fresh_cap) {
-    const size_t count = im.count, pad = im.pad;
-    const std::vector<RuleV4>& v4 = im.v4;
-    const std::vector<RuleV6>& v6 = im.v6;
-    const std::vector<int2>& info = im.info;
-    const std::vector<uint4>& fimg = im.fimg;
-    const bool tss = im.tss, tree_ok = im.tree_ok;
-    const TssFamily& f4 = im.f4;
-    const TssFamily& f6 = im.f6;
-    const std::vector<uint16_t>& fps = im.fps;
-    const std::vector<uint4>& timg = im.timg;
-    const TreeImage& t = im.t;
-    const uint32_t fam4 = im.fam4, fam6 = im.fam6, fam_all = im.fam_all, fam_x1idx = im.fam_x1idx;
-    const bool fwd4 = im.fwd4, fwd6 = im.fwd6;
-    // every image on the device before anything of the context changes (what is not taken over
-    // below is freed on return)
-    DevBuf<RuleV4> b_rv4;
-    DevBuf<RuleV6> b_rv6;
-    DevBuf<int2> b_rinfo;
-    DevBuf<uint4> b_fam, b_tt4, b_tt6, b_tree;
-    DevBuf<uint16_t> b_tfs;
-    DevBuf<TssGroup> b_tg4, b_tg6;
-    StatsBuf b_idx;
-    if (b_rv4.put(v4.data(), pad) || b_rv6.put(v6.data(), pad) || b_rinfo.put(info.data(), pad) ||
-        b_fam.put(fimg.data(), fimg.size()) ||
-        (tss && (b_tfs.put(fps.data(), fps.size()) ||
-                 b_tg4.put(f4.groups.data(), f4.groups.size()) ||
-                 b_tg6.put(f6.groups.data(), f6.groups.size()) ||
-                 b_tt4.put(f4.slots.data(), f4.slots.size()) ||
-                 b_tt6.put(f6.slots.data(), f6.slots.size()))) ||
-        (tree_ok && b_tree.put(timg.data(), timg.size())))
-        return -1;
+    DeviceTable next;   // dropped on an error return
+    if (next.upload(im) != 0) return -1;
     // the per-index totals are kept while they hold the new table
-    const bool grow = pad * 2 * kStatReps > c->stats_idx.cap;
-    if (grow && b_idx.zeros(pad * 2 * kStatReps) != 0) return -1;
+    StatsBuf idx;
+    const size_t idx_words = im.pad * 2 * kStatReps;
+    const bool grow = idx_words > c->stats.idx.cap;
+    if (grow && idx.zeros(idx_words) != 0) return -1;
     // previous batches may still read the table, on whichever stream they went
     if (c->last_stream) HIP_TRY(hipStreamSynchronize(c->last_stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (fresh) {
         // the reload's fresh statistics: the old table's per-index totals are dropped
-        if (c->stats_idx)
-            HIP_TRY(hipMemset(c->stats_idx, 0, c->stats_idx.cap * sizeof(unsigned long long)));
+        if (c->stats.idx)
+            HIP_TRY(hipMemset(c->stats.idx, 0, c->stats.idx.cap * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(&c->st->acc_stats[0][0], 0, sizeof(c->st->acc_stats)));
-        c->stats = std::move(*fresh);
-        c->cap = fresh_cap;
-        c->rinfo_host.clear();
+        c->stats.rule = std::move(*fresh);
+        c->stats.cap = fresh_cap;
     } else if (fold_stats_idx(c) != 0) {   // the old table's counts credited to their rule_ids
         return -1;
     }
-    // the swap (each move frees what the context held)
-    c->rv4 = std::move(b_rv4);
-    c->rv6 = std::move(b_rv6);
-    c->rinfo = std::move(b_rinfo);
-    if (grow) c->stats_idx = std::move(b_idx);
-    c->fam = std::move(b_fam);
-    c->fam4 = fam4;
-    c->fam6 = fam6;
-    c->fam_all = fam_all;
-    c->fam_x1idx = fam_x1idx;
-    c->fwd4 = fwd4;
-    c->fwd6 = fwd6;
-    // the kernel without look-back may have been chosen because a family could not forward
-    // under the old table: back to the full kernel until a launch under this one reports
-    c->no_lb = false;
-    c->lb_reset_k = c->k;
-    c->nrules = (uint32_t)count;
-    c->nrules_pad = (uint32_t)pad;
-    c->rinfo_host = info;
-    c->tfs = std::move(b_tfs);
-    c->tg4 = std::move(b_tg4);
-    c->tg6 = std::move(b_tg6);
-    c->tt4 = std::move(b_tt4);
-    c->tt6 = std::move(b_tt6);
-    c->tss = tss;
-    c->nfs = tss ? (uint32_t)(fps.size() / 8) : 0u;
-    c->ng4 = tss ? (uint32_t)f4.groups.size() : 0u;
-    c->ng6 = tss ? (uint32_t)f6.groups.size() : 0u;
-    c->tree = std::move(b_tree);
-    c->tree_ok = tree_ok;
+    // the swap (the moves free what the context held)
+    c->table = std::move(next);
+    if (grow) c->stats.idx = std::move(idx);
     const char* tl = getenv("UPE_GPU_TREE_LDS");   // diagnostic: 0 = the image stays in memory
     c->tree_stage = !(tl && tl[0] == '0');
-    c->tree_words = tree_ok ? (uint32_t)timg.size() : 0u;
-    c->tree_loff = tree_ok ? (uint32_t)(2 * t.nodes.size()) : 0u;
-    c->tree_info = tree_ok ? upe_rule_index_info_t{(uint64_t)t.nodes.size(), (uint64_t)t.leaves.size(),
-                                                   t.depth[0], t.depth[1], t.max_leaf,
-                                                   t.trees[0] | t.trees[1] << 16}
-                           : upe_rule_index_info_t{};
-    return publish(c);   // the DevState's pointers (stats, stats_idx)
+    // the kernel without look-back may have been chosen because a family could not forward
+    // under the old table: back to the full kernel until a launch under this one reports
+    c->lb.no_lb = false;
+    c->lb.reset_k = c->k;
+    return publish(c);   // the DevState's pointers (stats.rule, stats.idx)
 }
 
 int load_rules_impl(upe_gpu_ctx_t* c, const upe_rule_t* rules, size_t count,
                     StatsBuf* fresh, size_t fresh_cap) {
     upe_rule_image im;
-    if (build_image(rules, count, fresh ? fresh_cap : c->cap, im) != 0) return -1;
+    if (build_image(rules, count, fresh ? fresh_cap : c->stats.cap, im) != 0) return -1;
     return install_image(c, im, fresh, fresh_cap);
 }
 }  // namespace
@@ -3132,7 +3142,7 @@ extern "C" {
 
 extern "C" int upe_gpu_load_rules(upe_gpu_ctx_t* c, const upe_rule_t* rules, size_t count) {
     if (!c) return fail("null context");
-    if (count > c->cap) return fail("rule count exceeds the capacity given at open");
+    if (count > c->stats.cap) return fail("rule count exceeds the capacity given at open");
     if (count && !rules) return fail("null rules");
     DEV_SCOPE(c->device);
     return load_rules_impl(c, rules, count, nullptr, 0);
@@ -3191,15 +3201,18 @@ extern "C" int upe_gpu_tag_host(upe_gpu_ctx_t* c, int on) {
 
 extern "C" int upe_gpu_rule_index_kind(upe_gpu_ctx_t* c) {
     if (!c) return fail("null context");
-    return c->tss ? 1 : c->tree_ok ? 2 : 0;
+    return c->table.tss ? 1 : c->table.tree_ok ? 2 : 0;
 }
 
 extern "C" int upe_gpu_rule_index_info(upe_gpu_ctx_t* c, upe_rule_index_info_t* info) {
     if (!c || !info) return fail("null argument");
-    *info = c->tree_ok ? c->tree_info : upe_rule_index_info_t{};
+    *info = c->table.tree_ok ? c->table.tree_info : upe_rule_index_info_t{};
     return 0;
 }
 
+// All or nothing, as a rule reload is: the new snapshot is built (build_neigh_image, upe_rules.cpp)
+// and uploaded beside the old one, and only then moved into the context; on an error the context
+// keeps looking up in the old snapshot.
 int upe_gpu_load_neigh(upe_gpu_ctx_t* c, const upe_arp_entry_t* arp, size_t arp_capacity,
                        const upe_ndp_entry_t* ndp, size_t ndp_capacity) {
     if (!c) return fail("null context");
@@ -3209,79 +3222,15 @@ int upe_gpu_load_neigh(upe_gpu_ctx_t* c, const upe_arp_entry_t* arp, size_t arp_
     if ((arp_capacity && !arp) || (ndp_capacity && !ndp)) return fail("null table");
     if (arp_capacity > (1u << 30) || ndp_capacity > (1u << 30)) return fail("table too large");
     DEV_SCOPE(c->device);
-    // Keep only the entries a reference probe reaches (arp_get_mac, src/arp_table.c:55-80:
-    // home slot ip & (cap-1), linear probe, first valid match, stop at the first invalid slot).
-    std::vector<uint32_t> arp_keep;
-    for (size_t s0 = 0; s0 < arp_capacity; ++s0) {
-        if (!arp[s0].valid) continue;
-        const uint32_t ip = arp[s0].ip;
-        const size_t mask = arp_capacity - 1;
-        for (size_t i = 0, t = ip & mask; i < arp_capacity; ++i, t = (t + 1) & mask) {
-            if (!arp[t].valid) break;
-            if (arp[t].ip == ip) {
-                if (t == s0) arp_keep.push_back((uint32_t)s0);
-                break;
-            }
-        }
-    }
-    // Same for ndp_get_mac (src/ndp_table.c:6-17,67-86): home slot = XOR of the LE words.
-    std::vector<uint32_t> ndp_keep;
-    for (size_t s0 = 0; s0 < ndp_capacity; ++s0) {
-        if (!ndp[s0].valid) continue;
-        const uint8_t* ip = ndp[s0].ip;
-        const size_t mask = ndp_capacity - 1;
-        const size_t h = (le32(ip) ^ le32(ip + 4) ^ le32(ip + 8) ^ le32(ip + 12)) & mask;
-        for (size_t i = 0, t = h; i < ndp_capacity; ++i, t = (t + 1) & mask) {
-            if (!ndp[t].valid) break;
-            if (memcmp(ndp[t].ip, ip, 16) == 0) {
-                if (t == s0) ndp_keep.push_back((uint32_t)s0);
-                break;
-            }
-        }
-    }
-    // Place the reachable entries by three-choice cuckoo hashing at load factor <= 0.8.
-    std::vector<uint32_t> akey(arp_keep.size()), nkey(ndp_keep.size());
-    for (size_t j = 0; j < arp_keep.size(); ++j) akey[j] = arp[arp_keep[j]].ip;
-    std::vector<std::array<uint32_t, 4>> nwords(ndp_keep.size());
-    for (size_t j = 0; j < ndp_keep.size(); ++j) {
-        const uint8_t* ip = ndp[ndp_keep[j]].ip;
-        nwords[j] = {le32(ip), le32(ip + 4), le32(ip + 8), le32(ip + 12)};
-        nkey[j] = fold_v6(nwords[j].data());
-    }
-    uint32_t abits = 0, aseed = 0, nbits = 0, nseed = 0;
-    std::vector<int32_t> aslot, nslot;   // slot -> entry (index into *_keep), -1 empty
-    if (cuckoo3_place(akey, abits, aseed, aslot) != 0 || cuckoo3_place(nkey, nbits, nseed, nslot) != 0)
-        return fail("neighbour index: cuckoo placement failed");
-    std::vector<uint4> a(aslot.size(), make_uint4(0, 0, 0, 0));
-    for (size_t t = 0; t < aslot.size(); ++t) {
-        if (aslot[t] < 0) continue;
-        const upe_arp_entry_t& e = arp[arp_keep[aslot[t]]];
-        a[t] = make_uint4(e.ip, mac_lo(e.mac), mac_hi(e.mac) | (1u << 16), 0);
-    }
-    std::vector<uint4> b(2 * nslot.size(), make_uint4(0, 0, 0, 0));
-    for (size_t t = 0; t < nslot.size(); ++t) {
-        if (nslot[t] < 0) continue;
-        const upe_ndp_entry_t& e = ndp[ndp_keep[nslot[t]]];
-        const auto& w = nwords[nslot[t]];
-        b[2 * t] = make_uint4(w[0], w[1], w[2], w[3]);
-        b[2 * t + 1] = make_uint4(mac_lo(e.mac), mac_hi(e.mac) | (1u << 16), 0, 0);
-    }
-    if (a.empty()) a.push_back(make_uint4(0, 0, 0, 0));   // keep a valid allocation
-    if (b.empty()) b.resize(2, make_uint4(0, 0, 0, 0));
+    NeighImage im;
+    NeighTable next;   // dropped on an error return
+    if (build_neigh_image(arp, arp_capacity, ndp, ndp_capacity, im) != 0 || next.upload(im) != 0)
+        return -1;
     // the last batch's L1 outcome into the starting state before the tables change
     if (c->st && l1_sync(c) != 0) return -1;
     if (c->last_stream) HIP_TRY(hipStreamSynchronize(c->last_stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->arp.reset();   // both go before either comes back
-    c->ndp.reset();
-    if (c->arp.reserve(a.size(), a.size()) != 0 || c->ndp.reserve(b.size(), b.size()) != 0)
-        return -1;
-    HIP_TRY(hipMemcpy(c->arp, a.data(), a.size() * sizeof(uint4), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->ndp, b.data(), b.size() * sizeof(uint4), hipMemcpyHostToDevice));
-    c->arp_bits = abits;
-    c->arp_seed = aseed;
-    c->ndp_bits = nbits;
-    c->ndp_seed = nseed;
+    c->neigh = std::move(next);   // frees the old snapshot: nothing queued reads it any more
     if (c->st && refresh(c) != 0) return -1;   // does the L1 state agree with the new tables?
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
@@ -3362,55 +3311,54 @@ struct ProcessReq {
     size_t tx_base = 0;              // the launch's first packet in the caller's batch
 };
 
-TableShape table_shape(const upe_gpu_ctx* c) {
-    return TableShape{c->tss, c->nrules, c->nrules_pad, c->arp_bits, c->ndp_bits, c->nfs,
-                      c->tree_ok, c->tree_stage, c->tree_words, c->fam4, c->fam6, c->fam_all != 0};
-}
-
-// Timing sample: an event pair around `timing_span` consecutive calls, opened on every
-// timing_every-th call (samples never overlap).
+// Timing sample: an event pair around `span` consecutive calls, opened on every
+// every-th call (samples never overlap).
 int open_sample(upe_gpu_ctx* c, hipStream_t s) {
-    const bool open = c->timing && c->t_left == 0 &&
-                      (c->timing_calls % c->timing_every) == c->timing_phase;
-    if (c->timing) ++c->timing_calls;
+    upe_gpu_ctx::Timing& t = c->timing;
+    const bool open = t.on && t.left == 0 &&
+                      (t.calls % t.every) == t.phase;
+    if (t.on) ++t.calls;
     if (!open) return 0;
-    while (c->ev.size() < c->ev_used + 3) {
+    while (t.ev.size() < t.ev_used + 3) {
         hipEvent_t e;
         HIP_TRY(hipEventCreate(&e));
-        c->ev.push_back(e);
+        t.ev.push_back(e);
     }
-    HIP_TRY(hipEventRecord(c->ev[c->ev_used], s));
-    c->t_left = c->timing_span;
+    HIP_TRY(hipEventRecord(t.ev[t.ev_used], s));
+    t.left = t.span;
     return 0;
 }
 // mid: the sample's middle event was recorded (mid_sample)
 int close_sample(upe_gpu_ctx* c, hipStream_t s, bool mid) {
-    if (c->t_left && --c->t_left == 0) {
-        HIP_TRY(hipEventRecord(c->ev[c->ev_used + 2], s));
-        c->ev_mid.push_back(mid);
-        c->ev_used += 3;
-        c->timing_launches += c->timing_span;
+    upe_gpu_ctx::Timing& t = c->timing;
+    if (t.left && --t.left == 0) {
+        HIP_TRY(hipEventRecord(t.ev[t.ev_used + 2], s));
+        t.ev_mid.push_back(mid);
+        t.ev_used += 3;
+        t.launches += t.span;
     }
     return 0;
 }
 
 // Once a launch has been seen starting from agreeing L1 entries (or from an entry whose
 // family's index is empty), every later one does until the host changes tables or entries:
-// c->no_lb.
+// c->lb.no_lb.
 int settle_no_lb(upe_gpu_ctx* c) {
-    if (c->no_lb || !c->agree_h || !c->allow_nolb) return 0;
-    if (c->lb_sync && c->k > c->lb_reset_k && c->last_stream)
+    if (c->lb.no_lb || !c->lb.agree_h || !c->lb.allow_nolb) return 0;
+    if (c->lb.sync && c->k > c->lb.reset_k && c->last_stream)
         HIP_TRY(hipStreamSynchronize(c->last_stream));   // the previous launch's report
-    const unsigned long long v = __atomic_load_n(c->agree_h, __ATOMIC_ACQUIRE);
+    const unsigned long long v = __atomic_load_n(c->lb.agree_h, __ATOMIC_ACQUIRE);
     const unsigned long long tag = v >> 2;
-    if (tag != 0 && tag - 1 >= c->lb_reset_k && ((v & 1) || c->arp_bits == 0 || !c->fwd4) &&
-        ((v & 2) || c->ndp_bits == 0 || !c->fwd6))
-        c->no_lb = true;
+    if (tag != 0 && tag - 1 >= c->lb.reset_k &&
+        ((v & 1) || c->neigh.arp_bits == 0 || !c->table.fwd4) &&
+        ((v & 2) || c->neigh.ndp_bits == 0 || !c->table.fwd6))
+        c->lb.no_lb = true;
     return 0;
 }
 
 // The kernel's arguments but for the tiling and the ring's (process_impl sets those).
 Args fill_args(const upe_gpu_ctx* c, const ProcessReq& q, const LdsPlan& p) {
+    const DeviceTable& t = c->table;
     Args a;
     memset(&a, 0, sizeof a);   // every field a launch does not set stays null / zero
     a.frames = q.frames;
@@ -3422,43 +3370,43 @@ Args fill_args(const upe_gpu_ctx* c, const ProcessReq& q, const LdsPlan& p) {
     a.tx_base = (uint32_t)q.tx_base;
     a.flow_hash = q.flow_hash;
     a.hdr = reinterpret_cast<uint4*>(q.hdr);
-    a.rv4 = c->rv4;
-    a.rv6 = c->rv6;
-    a.rinfo = c->rinfo;
-    a.nrules_pad = c->nrules_pad;
-    a.fam = c->fam;
-    a.fam4 = c->fam4;
-    a.fam6 = c->fam6;
-    a.fam_x1idx = c->fam_x1idx;
-    a.tree = reinterpret_cast<const uint2*>(c->tree.p);
-    a.tree_loff = c->tree_loff;
+    a.rv4 = t.rv4;
+    a.rv6 = t.rv6;
+    a.rinfo = t.rinfo;
+    a.nrules_pad = t.nrules_pad;
+    a.fam = t.fam;
+    a.fam4 = t.fam4;
+    a.fam6 = t.fam6;
+    a.fam_x1idx = t.fam_x1idx;
+    a.tree = reinterpret_cast<const uint2*>(t.tree.p);
+    a.tree_loff = t.tree_loff;
     a.arp = arp_index(c);
     a.ndp = ndp_index(c);
     a.st = c->st;
     a.port_mac_lo = c->port_mac_lo;
     a.port_mac_hi = c->port_mac_hi;
     a.port_ip4 = c->port_ip4;
-    a.tg4 = c->tg4;
-    a.tg6 = c->tg6;
-    a.tt4 = c->tt4;
-    a.tt6 = c->tt6;
-    a.tfs = reinterpret_cast<const uint4*>(c->tfs.p);
-    a.ng4 = c->ng4;
-    a.ng6 = c->ng6;
-    a.tss = c->tss ? 1u : 0u;
+    a.tg4 = t.tg4;
+    a.tg6 = t.tg6;
+    a.tt4 = t.tt4;
+    a.tt6 = t.tt6;
+    a.tfs = reinterpret_cast<const uint4*>(t.tfs.p);
+    a.ng4 = t.ng4;
+    a.ng6 = t.ng6;
+    a.tss = t.tss ? 1u : 0u;
     a.pay = c->pay;
     a.paycap = c->paycap;
-    a.stats = c->stats;
-    a.stats_idx = c->stats_idx;
+    a.stats = c->stats.rule;
+    a.stats_idx = c->stats.idx;
     a.k6 = (uint32_t)(c->k % 6);
-    a.lb = c->lb;
-    a.defer = c->defer;
-    a.lb_spin = c->lb_spin;
+    a.lb = c->lb.flags;
+    a.defer = c->lb.defer;
+    a.lb_spin = c->lb.spin;
     a.lb_tag = (uint32_t)(c->k % kLbTagMod) + 1u;
-    a.agree_out = c->no_lb ? nullptr : c->agree_d;
+    a.agree_out = c->lb.no_lb ? nullptr : c->lb.agree_d;
     a.launch_tag = c->k + 1;
     // the plan's share (upe_plan.h)
-    a.gb = p.gb ? c->gb.p : nullptr;
+    a.gb = p.gb ? c->stats.gb.p : nullptr;
     a.gb_packed = p.gb_packed;
     a.arp_lds = p.arp_lds;
     a.ndp_lds = p.ndp_lds;
@@ -3474,9 +3422,9 @@ Args fill_args(const upe_gpu_ctx* c, const ProcessReq& q, const LdsPlan& p) {
 // upe_hist_reduce.
 int launch_group_by(upe_gpu_ctx* c, const uint32_t* d_verdict, size_t n, bool packed,
                     hipStream_t s) {
-    const GroupByPlan g = plan_group_by(c->nrules, n);
+    const GroupByPlan g = plan_group_by(c->table.nrules, n);
     const size_t part_words = (size_t)g.grid_x * g.nrules;
-    if (c->hist_part.reserve(part_words, part_words) != 0) return -1;
+    if (c->stats.hist_part.reserve(part_words, part_words) != 0) return -1;
     static std::atomic<uint64_t> hist_attr{0};   // 128 KB of dynamic LDS, once per device
     if (!(hist_attr.fetch_or(1ull << (c->device & 63)) & (1ull << (c->device & 63)))) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&upe_rule_hist<true>),
@@ -3490,13 +3438,16 @@ int launch_group_by(upe_gpu_ctx* c, const uint32_t* d_verdict, size_t n, bool pa
     const size_t lds = g.range * sizeof(unsigned long long);
     if (packed)
         hipLaunchKernelGGL(upe_rule_hist<true>, hg, dim3(kHistBlock), lds, s, d_verdict,
-                           c->gb.p, (uint32_t)n, g.nrules, c->hist_part.p, g.chunk, g.range);
+                           c->stats.gb.p, (uint32_t)n, g.nrules, c->stats.hist_part.p, g.chunk,
+                           g.range);
     else
         hipLaunchKernelGGL(upe_rule_hist<false>, hg, dim3(kHistBlock), lds, s, d_verdict,
-                           c->gb.p, (uint32_t)n, g.nrules, c->hist_part.p, g.chunk, g.range);
+                           c->stats.gb.p, (uint32_t)n, g.nrules, c->stats.hist_part.p, g.chunk,
+                           g.range);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(upe_hist_reduce, dim3((g.nrules + 255) / 256, kStatReps), dim3(256), 0, s,
-                       c->hist_part.p, g.grid_x, g.nrules, c->nrules_pad, c->stats_idx.p);
+                       c->stats.hist_part.p, g.grid_x, g.nrules, c->table.nrules_pad,
+                       c->stats.idx.p);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -3536,14 +3487,14 @@ int process_impl(upe_gpu_ctx_t* c, const ProcessReq& q) {
     // they went: a batch starts from the state the one before it left
     if (order_on(c, s) != 0 || open_sample(c, s) != 0) return -1;
     if (c->k > 0 && c->k % kLbTagMod == 0)   // tags wrap: no flag may carry this launch's tag
-        HIP_TRY(hipMemsetAsync(c->lb, 0, c->lb.cap * sizeof(uint32_t), s));
+        HIP_TRY(hipMemsetAsync(c->lb.flags, 0, c->lb.flags.cap * sizeof(uint32_t), s));
     // 4. plan (upe_plan.h)
     if (settle_no_lb(c) != 0) return -1;
     const bool emit = q.hdr != nullptr && n > 0;
     const PlanReq pq{n, emit, q.flow_hash != nullptr, q.tx != nullptr, host,
                      q.ring ? q.ring->per : 0, q.ring && q.ring->done};
-    const LdsPlan p = plan_lds(table_shape(c), pq, c->no_lb);
-    if (p.gb && c->gb.reserve(n, (n + n / 4 + 64) & ~(size_t)3) != 0) return -1;   // either form
+    const LdsPlan p = plan_lds(c->table.shape(c->neigh, c->tree_stage), pq, c->lb.no_lb);
+    if (p.gb && c->stats.gb.reserve(n, (n + n / 4 + 64) & ~(size_t)3) != 0) return -1;   // either form
     // 5. the arguments
     Args a = fill_args(c, q, p);
     // persistent grid: the workgroups the chip holds at once
@@ -3552,7 +3503,7 @@ int process_impl(upe_gpu_ctx_t* c, const ProcessReq& q) {
     if (grid_cap == 0) return -1;
     // the census of the no-look-back counterpart now as well, so that the switch to it (a few
     // launches later) does not put a synchronous census launch in the middle of a batch stream
-    if (p.lean && !c->no_lb) {
+    if (p.lean && !c->lb.no_lb) {
         Variant nolb = var;
         nolb.nolb = true;
         if (resident_grid(c, nolb, p.lds, s) == 0) return -1;
@@ -3587,8 +3538,8 @@ int process_impl(upe_gpu_ctx_t* c, const ProcessReq& q) {
     c->last_grid = t.grid;
     // 8. the group-by; before it the sample's middle event, between the classify launch and the
     // group-by (last call of the sample only; launches without a group-by have none)
-    const bool mid = c->t_left == 1 && p.gb;
-    if (mid) HIP_TRY(hipEventRecord(c->ev[c->ev_used + 1], s));
+    const bool mid = c->timing.left == 1 && p.gb;
+    if (mid) HIP_TRY(hipEventRecord(c->timing.ev[c->timing.ev_used + 1], s));
     if (p.gb && launch_group_by(c, q.verdict, n, p.gb_packed != 0, s) != 0) return -1;
     // 9., 10.
     if (close_sample(c, s, mid) != 0) return -1;
@@ -3669,10 +3620,10 @@ int host_roundtrip(upe_gpu_ctx_t* c, uint8_t* h_frames, size_t frames_bytes,
     // emit: whole 64-packet groups per chunk, so that each chunk's compacted records (relative to
     // its first packet) land where the batch's own layout puts them
     if (emit) chunk = std::max<size_t>(64, chunk & ~(size_t)63);
-    if (!c->s_in) {
-        HIP_TRY(hipStreamCreateWithFlags(&c->s_in, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&c->s_out, hipStreamNonBlocking));
-        for (auto& sl : c->hs) {
+    if (!c->host.s_in) {
+        HIP_TRY(hipStreamCreateWithFlags(&c->host.s_in, hipStreamNonBlocking));
+        HIP_TRY(hipStreamCreateWithFlags(&c->host.s_out, hipStreamNonBlocking));
+        for (auto& sl : c->host.slots) {
             HIP_TRY(hipEventCreateWithFlags(&sl.in_done, hipEventDisableTiming));
             HIP_TRY(hipEventCreateWithFlags(&sl.k_done, hipEventDisableTiming));
             HIP_TRY(hipEventCreateWithFlags(&sl.out_done, hipEventDisableTiming));
@@ -3684,27 +3635,28 @@ int host_roundtrip(upe_gpu_ctx_t* c, uint8_t* h_frames, size_t frames_bytes,
         return 0;
     }
     const bool apply = emit && apply_threads >= 0;
-    if (apply && apply_threads > 0 && (!c->pool || c->pool->th.size() != (size_t)apply_threads)) {
+    if (apply && apply_threads > 0 &&
+        (!c->host.pool || c->host.pool->th.size() != (size_t)apply_threads)) {
         std::vector<int> cpus(CPU_SETSIZE);
         const int k = upe_gpu_local_cpus(c->device, cpus.data(), cpus.size(), nullptr);
         cpus.resize(k > 0 ? (size_t)k : 0);
-        c->pool.reset();
-        c->pool.reset(new ApplyPool((unsigned)apply_threads, cpus));
+        c->host.pool.reset();
+        c->host.pool.reset(new ApplyPool((unsigned)apply_threads, cpus));
     }
     // Whatever happens below, no copy into the caller's buffers is left in flight on return.
     struct Drain {
         upe_gpu_ctx* c;
         ~Drain() {
-            (void)hipStreamSynchronize(c->s_in);
+            (void)hipStreamSynchronize(c->host.s_in);
             (void)hipStreamSynchronize(c->stream);
-            (void)hipStreamSynchronize(c->s_out);
-            for (auto& sl : c->hs) sl.busy = false;
+            (void)hipStreamSynchronize(c->host.s_out);
+            for (auto& sl : c->host.slots) sl.busy = false;
         }
     } drain{c};
-    const size_t nslots = c->host_slots;
+    const size_t nslots = c->host.nslots;
     // copies back on their own stream: both link directions at once (issuing them on the copy-in
     // stream after the next chunk's copy-in measured slower: B 332-344 vs 480 Mpps in place)
-    hipStream_t s_back = c->s_out;
+    hipStream_t s_back = c->host.s_out;
     const size_t lag = 2;   // emit: chunk k - lag is applied while chunk k is issued
     struct Done {
         size_t s, e, slot;
@@ -3714,7 +3666,7 @@ int host_roundtrip(upe_gpu_ctx_t* c, uint8_t* h_frames, size_t frames_bytes,
     // apply chunk d's records (and copy back its answered ARP requests, rewritten in place in
     // the device slot, which the reference transmits from b->data, src/worker.c:40-52)
     auto finish = [&](const Done& d) -> int {
-        auto& sl = c->hs[d.slot];
+        auto& sl = c->host.slots[d.slot];
         HIP_TRY(hipEventSynchronize(sl.out_done));
         std::atomic<bool> replies{false};
         auto job = [&](unsigned t, unsigned T) {
@@ -3733,7 +3685,7 @@ int host_roundtrip(upe_gpu_ctx_t* c, uint8_t* h_frames, size_t frames_bytes,
             }
             if (r) replies.store(true, std::memory_order_relaxed);
         };
-        if (c->pool && apply && apply_threads > 0) c->pool->run(job);
+        if (c->host.pool && apply && apply_threads > 0) c->host.pool->run(job);
         else job(0, 1);
         if (replies.load())
             for (size_t i = d.s; i < d.e; ++i)
@@ -3748,7 +3700,7 @@ int host_roundtrip(upe_gpu_ctx_t* c, uint8_t* h_frames, size_t frames_bytes,
     // a chunk's copy-back (verdicts + records, or verdicts + the rewritten span), once its kernel
     // is queued
     auto issue_back = [&](size_t s, size_t e, size_t slot, uint64_t lo, uint64_t wb) -> int {
-        auto& sb = c->hs[slot];
+        auto& sb = c->host.slots[slot];
         const size_t m = e - s;
         HIP_TRY(hipStreamWaitEvent(s_back, sb.k_done, 0));
         HIP_TRY(hipMemcpyAsync(h_verdict + s, sb.verdict, m * sizeof(uint32_t),
@@ -3784,7 +3736,7 @@ int host_roundtrip(upe_gpu_ctx_t* c, uint8_t* h_frames, size_t frames_bytes,
             return fail("a frame window runs past frames_bytes (UPE_FRAME_TAIL bytes must follow "
                         "every frame start)");
         const size_t si = k % nslots;
-        auto& sl = c->hs[si];
+        auto& sl = c->host.slots[si];
         if (emit && pending.size() >= lag) {   // the oldest finished before its slot is reused
             if (finish(pending.front()) != 0) return -1;
             pending.erase(pending.begin());
@@ -3809,13 +3761,13 @@ int host_roundtrip(upe_gpu_ctx_t* c, uint8_t* h_frames, size_t frames_bytes,
         // earlier chunk's frames as they were before they were processed.  (Emit mode copies
         // no frame bytes back.)
         if (!emit)
-            for (auto& other : c->hs)
+            for (auto& other : c->host.slots)
                 if (&other != &sl && other.busy && other.lo < hi && lo < other.wb)
-                    HIP_TRY(hipStreamWaitEvent(c->s_in, other.out_done, 0));
-        HIP_TRY(hipMemcpyAsync(sl.frames, h_frames + lo, span, hipMemcpyHostToDevice, c->s_in));
+                    HIP_TRY(hipStreamWaitEvent(c->host.s_in, other.out_done, 0));
+        HIP_TRY(hipMemcpyAsync(sl.frames, h_frames + lo, span, hipMemcpyHostToDevice, c->host.s_in));
         HIP_TRY(hipMemcpyAsync(sl.desc, h_desc + s, m * sizeof(uint64_t), hipMemcpyHostToDevice,
-                               c->s_in));
-        HIP_TRY(hipEventRecord(sl.in_done, c->s_in));
+                               c->host.s_in));
+        HIP_TRY(hipEventRecord(sl.in_done, c->host.s_in));
         HIP_TRY(hipStreamWaitEvent(c->stream, sl.in_done, 0));
         // the descriptors keep their offsets relative to h_frames: hand the kernel a base that
         // maps offset lo onto the slot (lo is a multiple of 16, so the base stays aligned)
@@ -4194,39 +4146,39 @@ int upe_gpu_process_segmented(upe_gpu_ctx_t* c, uint8_t* d_frames, const uint64_
     DEV_SCOPE(c->device);
     hipStream_t s = pick(c, stream);
     // 1. mark and list the table-writing control packets, in packet order
-    if (n > c->ctrl_index.cap) {   // (the last one made: all are there when it is)
-        c->ctrl_marks.reset();
-        c->ctrl_index.reset();
-        if (c->ctrl_count.reserve(1, 1) != 0 ||   // once
-            c->ctrl_marks.reserve(n, n) != 0 || c->ctrl_index.reserve(n, n) != 0)
+    if (n > c->seg.index.cap) {   // (the last one made: all are there when it is)
+        c->seg.marks.reset();
+        c->seg.index.reset();
+        if (c->seg.count.reserve(1, 1) != 0 ||   // once
+            c->seg.marks.reserve(n, n) != 0 || c->seg.index.reserve(n, n) != 0)
             return -1;
     }
     hipLaunchKernelGGL(upe_ctrl_mark, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s,
-                       d_frames, d_desc, (uint32_t)n, c->ctrl_marks);
+                       d_frames, d_desc, (uint32_t)n, c->seg.marks);
     HIP_TRY(hipGetLastError());
-    if (upe_gpu_compact(c, c->ctrl_marks, n, 1u, c->ctrl_index, c->ctrl_count, s) != 0) return -1;
+    if (upe_gpu_compact(c, c->seg.marks, n, 1u, c->seg.index, c->seg.count, s) != 0) return -1;
     uint64_t cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&cnt, c->ctrl_count, sizeof cnt, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&cnt, c->seg.count, sizeof cnt, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (cnt == 0) return upe_gpu_process(c, d_frames, d_desc, d_verdict, n, stream);
     // 2. their bytes, gathered before any segment runs (the ARP reply is built in place)
-    if (cnt > c->ctrl_lens.cap) {   // (the last one made)
-        c->ctrl_win.reset();
-        c->ctrl_lens.reset();
-        if (c->ctrl_win.reserve(cnt * kCtrlWin, cnt * kCtrlWin) != 0 ||
-            c->ctrl_lens.reserve(cnt, cnt) != 0)
+    if (cnt > c->seg.lens.cap) {   // (the last one made)
+        c->seg.win.reset();
+        c->seg.lens.reset();
+        if (c->seg.win.reserve(cnt * kCtrlWin, cnt * kCtrlWin) != 0 ||
+            c->seg.lens.reserve(cnt, cnt) != 0)
             return -1;
     }
     hipLaunchKernelGGL(upe_ctrl_gather, dim3((uint32_t)cnt), dim3(kCtrlWin), 0, s, d_frames,
-                       d_desc, c->ctrl_index, c->ctrl_win, c->ctrl_lens);
+                       d_desc, c->seg.index, c->seg.win, c->seg.lens);
     HIP_TRY(hipGetLastError());
     std::vector<uint32_t> idx(cnt), lens(cnt);
     std::vector<uint8_t> win(cnt * kCtrlWin);
-    HIP_TRY(hipMemcpyAsync(idx.data(), c->ctrl_index, cnt * sizeof(uint32_t),
+    HIP_TRY(hipMemcpyAsync(idx.data(), c->seg.index, cnt * sizeof(uint32_t),
                            hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(lens.data(), c->ctrl_lens, cnt * sizeof(uint32_t),
+    HIP_TRY(hipMemcpyAsync(lens.data(), c->seg.lens, cnt * sizeof(uint32_t),
                            hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(win.data(), c->ctrl_win, win.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(win.data(), c->seg.win, win.size(), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     // 3. segments: up to and including each control packet, then its table write
     size_t start = 0, writes = 0;
@@ -4384,9 +4336,9 @@ int upe_gpu_reset_stats(upe_gpu_ctx_t* c) {
         HIP_TRY(hipMemsetAsync(&b->n, 0, sizeof(b->n), c->stream));
     }
     HIP_TRY(hipMemsetAsync(&c->st->acc_stats[0][0], 0, sizeof(c->st->acc_stats), c->stream));
-    HIP_TRY(hipMemsetAsync(c->stats, 0, c->cap * 2 * sizeof(unsigned long long), c->stream));
-    if (c->stats_idx)
-        HIP_TRY(hipMemsetAsync(c->stats_idx, 0, c->stats_idx.cap * sizeof(unsigned long long),
+    HIP_TRY(hipMemsetAsync(c->stats.rule, 0, c->stats.cap * 2 * sizeof(unsigned long long), c->stream));
+    if (c->stats.idx)
+        HIP_TRY(hipMemsetAsync(c->stats.idx, 0, c->stats.idx.cap * sizeof(unsigned long long),
                                c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_batch = false;
@@ -4398,15 +4350,15 @@ int upe_gpu_timing_span(upe_gpu_ctx_t* c, int every, int span) {
     if (span < 1) return fail("span must be at least 1");
     DEV_SCOPE(c->device);
     HIP_TRY(hipDeviceSynchronize());
-    c->ev_used = 0;   // the pool is kept for reuse
-    c->ev_mid.clear();
-    c->timing = every > 0;
-    c->timing_every = every > 0 ? (uint32_t)every : 1u;
-    c->timing_phase = c->timing_every / 2;   // not the first call: it starts from an idle queue
-    c->timing_span = (uint32_t)span;
-    c->timing_calls = 0;
-    c->t_left = 0;
-    c->timing_launches = 0;
+    c->timing.ev_used = 0;   // the pool is kept for reuse
+    c->timing.ev_mid.clear();
+    c->timing.on = every > 0;
+    c->timing.every = every > 0 ? (uint32_t)every : 1u;
+    c->timing.phase = c->timing.every / 2;   // not the first call: it starts from an idle queue
+    c->timing.span = (uint32_t)span;
+    c->timing.calls = 0;
+    c->timing.left = 0;
+    c->timing.launches = 0;
     return 0;
 }
 
@@ -4419,21 +4371,21 @@ int upe_gpu_timing_read(upe_gpu_ctx_t* c, double* classify_ms, double* finalize_
     if (!c) return fail("null context");
     DEV_SCOPE(c->device);
     double a = 0, b = 0;
-    for (size_t j = 0, k = 0; j + 3 <= c->ev_used; j += 3, ++k) {
-        HIP_TRY(hipEventSynchronize(c->ev[j + 2]));
+    for (size_t j = 0, k = 0; j + 3 <= c->timing.ev_used; j += 3, ++k) {
+        HIP_TRY(hipEventSynchronize(c->timing.ev[j + 2]));
         float x = 0, y = 0;
-        if (c->ev_mid[k]) {
-            HIP_TRY(hipEventElapsedTime(&x, c->ev[j], c->ev[j + 1]));
-            HIP_TRY(hipEventElapsedTime(&y, c->ev[j + 1], c->ev[j + 2]));
+        if (c->timing.ev_mid[k]) {
+            HIP_TRY(hipEventElapsedTime(&x, c->timing.ev[j], c->timing.ev[j + 1]));
+            HIP_TRY(hipEventElapsedTime(&y, c->timing.ev[j + 1], c->timing.ev[j + 2]));
         } else {
-            HIP_TRY(hipEventElapsedTime(&x, c->ev[j], c->ev[j + 2]));
+            HIP_TRY(hipEventElapsedTime(&x, c->timing.ev[j], c->timing.ev[j + 2]));
         }
         a += x;
         b += y;
     }
     if (classify_ms) *classify_ms = a;
     if (finalize_ms) *finalize_ms = b;
-    if (launches) *launches = c->timing_launches;
+    if (launches) *launches = c->timing.launches;
     return 0;
 }
 

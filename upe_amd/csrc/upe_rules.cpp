@@ -1,8 +1,9 @@
 // upe_rules.cpp — the rule compiler of libupe_gpu: rule_t tables -> the images the classify
 // kernels read (upe_dev.h): the RuleV4 / RuleV6 words, the family lists, the tuple-space index,
-// the decision-tree forest; and the host walk of the tree (upe_rules_match_host).  Plain C++,
-// host memory only: no context, no GPU, any thread.  tools/rules_san.cpp runs it under the host
-// sanitizers (`make rules-san`).
+// the decision-tree forest; and the host walk of the tree (upe_rules_match_host).  Also the
+// neighbour snapshot upe_gpu_load_neigh uploads (build_neigh_image).  Plain C++, host memory
+// only: no context, no GPU, any thread.  tools/rules_san.cpp and tools/neigh_san.cpp run it under
+// the host sanitizers (`make rules-san`, `make neigh-san`).
 #include "upe_rules.h"
 
 #include <stdio.h>
@@ -67,6 +68,73 @@ int cuckoo3_place(const std::vector<uint32_t>& key, uint32_t& bits, uint32_t& se
         }
     }
     return -1;
+}
+
+namespace {
+// The slots a reference probe reaches (arp_get_mac, src/arp_table.c:55-80; ndp_get_mac,
+// src/ndp_table.c:67-86): from the key's home slot, a linear probe answers with the first valid
+// entry of the same key and stops at the first invalid slot.
+template <class E, class Home, class Same>
+std::vector<uint32_t> reachable(const E* e, size_t cap, Home home, Same same) {
+    std::vector<uint32_t> keep;
+    const size_t mask = cap - 1;
+    for (size_t s0 = 0; s0 < cap; ++s0) {
+        if (!e[s0].valid) continue;
+        for (size_t i = 0, t = home(e[s0]) & mask; i < cap; ++i, t = (t + 1) & mask) {
+            if (!e[t].valid) break;
+            if (same(e[t], e[s0])) {
+                if (t == s0) keep.push_back((uint32_t)s0);
+                break;
+            }
+        }
+    }
+    return keep;
+}
+}  // namespace
+
+// (upe_rules.h)
+int build_neigh_image(const upe_arp_entry_t* arp, size_t arp_cap, const upe_ndp_entry_t* ndp,
+                      size_t ndp_cap, NeighImage& im) {
+    const std::vector<uint32_t> arp_keep = reachable(
+        arp, arp_cap, [](const upe_arp_entry_t& e) { return (size_t)e.ip; },
+        [](const upe_arp_entry_t& a, const upe_arp_entry_t& b) { return a.ip == b.ip; });
+    // ndp_hash (src/ndp_table.c:6-17): home slot = XOR of the LE words
+    const std::vector<uint32_t> ndp_keep = reachable(
+        ndp, ndp_cap,
+        [](const upe_ndp_entry_t& e) {
+            return (size_t)(le32(e.ip) ^ le32(e.ip + 4) ^ le32(e.ip + 8) ^ le32(e.ip + 12));
+        },
+        [](const upe_ndp_entry_t& a, const upe_ndp_entry_t& b) { return memcmp(a.ip, b.ip, 16) == 0; });
+    // Place the reachable entries by three-choice cuckoo hashing at load factor <= 0.8.
+    std::vector<uint32_t> akey(arp_keep.size()), nkey(ndp_keep.size());
+    for (size_t j = 0; j < arp_keep.size(); ++j) akey[j] = arp[arp_keep[j]].ip;
+    std::vector<std::array<uint32_t, 4>> nwords(ndp_keep.size());
+    for (size_t j = 0; j < ndp_keep.size(); ++j) {
+        const uint8_t* ip = ndp[ndp_keep[j]].ip;
+        nwords[j] = {le32(ip), le32(ip + 4), le32(ip + 8), le32(ip + 12)};
+        nkey[j] = fold_v6(nwords[j].data());
+    }
+    std::vector<int32_t> aslot, nslot;   // slot -> entry (index into *_keep), -1 empty
+    if (cuckoo3_place(akey, im.arp_bits, im.arp_seed, aslot) != 0 ||
+        cuckoo3_place(nkey, im.ndp_bits, im.ndp_seed, nslot) != 0)
+        return fail("neighbour index: cuckoo placement failed");
+    im.arp.assign(aslot.size(), make_uint4(0, 0, 0, 0));
+    for (size_t t = 0; t < aslot.size(); ++t) {
+        if (aslot[t] < 0) continue;
+        const upe_arp_entry_t& e = arp[arp_keep[aslot[t]]];
+        im.arp[t] = make_uint4(e.ip, mac_lo(e.mac), mac_hi(e.mac) | (1u << 16), 0);
+    }
+    im.ndp.assign(2 * nslot.size(), make_uint4(0, 0, 0, 0));
+    for (size_t t = 0; t < nslot.size(); ++t) {
+        if (nslot[t] < 0) continue;
+        const upe_ndp_entry_t& e = ndp[ndp_keep[nslot[t]]];
+        const auto& w = nwords[nslot[t]];
+        im.ndp[2 * t] = make_uint4(w[0], w[1], w[2], w[3]);
+        im.ndp[2 * t + 1] = make_uint4(mac_lo(e.mac), mac_hi(e.mac) | (1u << 16), 0, 0);
+    }
+    if (im.arp.empty()) im.arp.push_back(make_uint4(0, 0, 0, 0));   // keep a valid allocation
+    if (im.ndp.empty()) im.ndp.resize(2, make_uint4(0, 0, 0, 0));
+    return 0;
 }
 
 }  // namespace upe

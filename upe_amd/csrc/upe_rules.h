@@ -1,6 +1,7 @@
 // upe_rules.h — the rule compiler (upe_rules.cpp, plain C++: no GPU, any thread): what
-// upe_gpu.hip installs into a context (struct upe_rule_image, build_image) and the cuckoo
-// placement upe_gpu_load_neigh shares with it.  The extern "C" entry points of the compiler
+// upe_gpu.hip installs into a context (struct upe_rule_image, build_image) and the neighbour
+// snapshot upe_gpu_load_neigh uploads (NeighImage, build_neigh_image, with the cuckoo placement
+// it shares with the compiler).  The extern "C" entry points of the compiler
 // (upe_rules_compile, upe_rules_image_free, upe_rules_match_host) are in include/upe_gpu.h.
 #ifndef UPE_RULES_H
 #define UPE_RULES_H
@@ -61,6 +62,18 @@ UPE_INTERNAL int build_image(const upe_rule_t* rules, size_t count, size_t cap, 
 // 2^bits >= 1.25 n slots, random-walk eviction, seeds tried, then doubles.  bits = 0 for no keys.
 UPE_INTERNAL int cuckoo3_place(const std::vector<uint32_t>& key, uint32_t& bits, uint32_t& seed,
                                std::vector<int32_t>& slot);
+
+// The neighbour snapshot a context looks up in (NeighIndex, upe_gpu.hip): each family's slot
+// array and its placement.  Host memory only; an empty family keeps one zero slot (bits 0).
+struct NeighImage {
+    std::vector<uint4> arp, ndp;
+    uint32_t arp_bits = 0, arp_seed = 0, ndp_bits = 0, ndp_seed = 0;
+};
+
+// Build the snapshot of the reference's slot arrays (power-of-two capacities, or 0): the entries
+// a reference probe reaches, placed by cuckoo3_place.  0, or -1 (upe_gpu_last_error()).
+UPE_INTERNAL int build_neigh_image(const upe_arp_entry_t* arp, size_t arp_cap,
+                                   const upe_ndp_entry_t* ndp, size_t ndp_cap, NeighImage& im);
 
 }  // namespace upe
 
