@@ -1,7 +1,7 @@
 // The neighbour snapshot builder (build_neigh_image, upe_amd/csrc/upe_rules.cpp) under the host
 // sanitizers, stand-alone: `make -C upe_amd/csrc neigh-san` builds this file with it
 // (-fsanitize=address,undefined) and runs it.  Deterministic slot arrays go through the builder;
-// every stored address and as many absent ones are then looked up in the image the way the
+// every stored address, as many absent ones and the all-zero address are then looked up in the image the way the
 // kernels do (the key's three candidate slots; a slot hits when it is used and holds the key) and
 // in the slot array the way the reference does (arp_get_mac, src/arp_table.c:55-80, ndp_get_mac,
 // src/ndp_table.c:67-86: from the home slot, linearly, the first valid entry of the key, nothing
@@ -159,6 +159,9 @@ static int check(const char* what, const Table<F>& tab) {
         q.push_back(k);
         ++absent;
     }
+    // the all-zero address (0.0.0.0 / ::) where the table lacks it: the key every empty slot of
+    // the image holds, so only the slots' used bit makes it miss
+    if (!stored.count(Key{})) q.push_back(Key{});
     size_t hits = 0;
     for (size_t i = 0; i < q.size(); ++i) {
         Mac got = {}, want = {};
@@ -222,6 +225,21 @@ static int family() {
         t.put(5, homed<F>(8, 2, 3));
         bad |= check("one address in two valid slots", t);
     }
+    {   // a valid entry for 0.0.0.0 / :: (an ARP probe makes the reference call arp_update(0, sha)):
+        // alone, and inside a chain that wraps (homes 7, 7, 0 = the zero address, 0)
+        Table<F> t(8);
+        t.insert(Key{});
+        if (!t.t[0].valid) return fprintf(stderr, "the zero address is not at slot 0\n"), 1;
+        bad |= check("the zero address alone", t);
+        Table<F> c(8);
+        c.insert(homed<F>(8, 7, 1));
+        c.insert(homed<F>(8, 7, 2));
+        c.insert(Key{});
+        c.insert(homed<F>(8, 0, 3));
+        if (!c.t[1].valid || F::key(c.t[1]) != Key{} || !c.t[2].valid)
+            return fprintf(stderr, "the zero address is not inside the chain\n"), 1;
+        bad |= check("the zero address inside a chain", c);
+    }
     {   // 4096 slots at about 0.7: inserted as the reference does, then holes knocked into the
         // chains (entries behind them become unreachable) and some of those keys inserted again
         // (the copy in the hole shadows the one behind it)
@@ -268,6 +286,21 @@ static int ndp_collisions() {
         t.insert(b);
     }
     int bad = check("addresses of one fold_v6", t);
+    {   // a fourth: the load fails, at once (not after a search through every size and seed)
+        Table<Ndp> f = t;
+        Key b = {0, a[1] + 3, a[2] ^ (3u << 8), a[3] + 21};
+        const uint32_t zero[4] = {0, b[1], b[2], b[3]};
+        b[0] = (fold_v6(a.data()) ^ fold_v6(zero)) * inv;
+        f.insert(b);
+        size_t valid = 0;
+        for (const auto& e : f.t) valid += e.valid;
+        NeighImage im;
+        g_msg[0] = 0;
+        if (valid != 4 || fold_v6(b.data()) != fold_v6(a.data()) ||
+            Ndp::build(f.t.data(), f.t.size(), im) == 0 || !strstr(g_msg, "placement"))
+            return fprintf(stderr, "four addresses of one fold_v6: no placement error (%s)\n", g_msg), 1;
+        printf("ndp four addresses of one fold_v6: %s\n", g_msg);
+    }
     // the same words in another order: equal XOR, so one home slot, one chain
     Table<Ndp> x(16);
     const uint32_t w[4] = {0x20010DB8u, 0x00000001u, 0xA5A50000u, 0x0000C3C3u};

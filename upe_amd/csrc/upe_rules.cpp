@@ -27,6 +27,15 @@ int cuckoo3_place(const std::vector<uint32_t>& key, uint32_t& bits, uint32_t& se
     bits = 0;
     seed = 0;
     if (n == 0) return 0;
+    // Equal keys share their three candidate slots under every seed and at every size: a fourth
+    // can never be placed.  Fail now: the search below would try every seed at every size up to
+    // 2^31 slots first (terabytes of slot-array clears) before it gave up.
+    {
+        std::vector<uint32_t> sorted(key);
+        std::sort(sorted.begin(), sorted.end());
+        for (size_t j = 3; j < n; ++j)
+            if (sorted[j] == sorted[j - 3]) return -1;
+    }
     bits = 1;
     while (((size_t)1 << bits) * 4 < n * 5) ++bits;
     for (; bits <= 31; ++bits) {
@@ -117,7 +126,8 @@ int build_neigh_image(const upe_arp_entry_t* arp, size_t arp_cap, const upe_ndp_
     std::vector<int32_t> aslot, nslot;   // slot -> entry (index into *_keep), -1 empty
     if (cuckoo3_place(akey, im.arp_bits, im.arp_seed, aslot) != 0 ||
         cuckoo3_place(nkey, im.ndp_bits, im.ndp_seed, nslot) != 0)
-        return fail("neighbour index: cuckoo placement failed");
+        return fail("neighbour index: cuckoo placement failed (at most three reachable IPv6 "
+                    "addresses may share one fold_v6)");
     im.arp.assign(aslot.size(), make_uint4(0, 0, 0, 0));
     for (size_t t = 0; t < aslot.size(); ++t) {
         if (aslot[t] < 0) continue;

@@ -60,6 +60,7 @@ UPE_INTERNAL int build_image(const upe_rule_t* rules, size_t count, size_t cap, 
 
 // Three-choice cuckoo placement of the neighbour indexes' keys (slot1 / slot2 / slot3): starts at
 // 2^bits >= 1.25 n slots, random-walk eviction, seeds tried, then doubles.  bits = 0 for no keys.
+// -1, at once, when more than three keys are equal (they share all three slots at every size).
 UPE_INTERNAL int cuckoo3_place(const std::vector<uint32_t>& key, uint32_t& bits, uint32_t& seed,
                                std::vector<int32_t>& slot);
 
