@@ -556,6 +556,107 @@ int upe_gpu_process_rss(upe_gpu_ctx_t *ctx, uint8_t *d_frames, const uint64_t *d
                         uint32_t *d_verdict, uint32_t *d_flow_hash, size_t n, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Ingress batch: a burst of pktbuf handles gathered on the device                             */
+/* ------------------------------------------------------------------------------------------ */
+/* The first stage: from what the reference hands a worker — a burst of pktbuf_t * handles into a
+ * pool of fixed-size buffers (include/pktbuf.h:8-14, src/worker.c:255-307) — to the "Batch
+ * layout" every other call here starts from, without the host touching a frame byte.  A handle
+ * is passed as its buffer index (b - pool->buffers).
+ *
+ * The pool.  Buffer s is the `stride` bytes at pool + s * stride: a 64-bit timestamp at 0, a
+ * 64-bit len at 8 and stride - 16 data bytes from 16 (pktbuf_t with stride = sizeof(pktbuf_t) =
+ * 2064; other strides serve small pools).  stride is a multiple of 16 and at least
+ * 16 + UPE_FRAME_TAIL; pool_bytes is at least stride and at most 2^36; pool is 16-byte aligned,
+ * in device memory or in host memory from upe_gpu_host_alloc / upe_gpu_host_register.  The
+ * kernels only load from it.  A slot may appear more than once, and slots need not ascend.
+ *
+ * A handle is bad when (uint64_t)s * stride + stride > pool_bytes (its buffer is then not
+ * read), or its len > stride - 16, or its len > 65535; len is compared as 64 bits.  A bad handle
+ * keeps its position k: it gets a descriptor of len 0 (offset k * UPE_HDR_WINDOW in WINDOW mode,
+ * 16 in REF and FULL mode), takes 0 bytes of d_out in FULL mode and an all-zero window in WINDOW
+ * mode, is never a control packet, and is counted in `bad`; its timestamp is the buffer's, or 0
+ * when the slot lies outside the pool.  The caller looks at info.bad before classifying.
+ *
+ * Modes.
+ *   UPE_INGRESS_REF     nothing is copied: d_desc[k] = UPE_DESC(s_k * stride + 16, len_k),
+ *                       relative to pool; the caller classifies the frames where they lie.
+ *                       bytes = need = 0.
+ *   UPE_INGRESS_WINDOW  d_out + k * UPE_HDR_WINDOW receives the frame's first
+ *                       min(len_k, UPE_HDR_WINDOW) bytes, then zeros to the window's end;
+ *                       d_desc[k] = UPE_DESC(k * UPE_HDR_WINDOW, len_k) — the staging layout of
+ *                       upe_gpu_worker_run.  Needs out_bytes >= n * UPE_HDR_WINDOW;
+ *                       bytes = need = n * UPE_HDR_WINDOW.
+ *   UPE_INGRESS_FULL    the packing rule of upe_gpu_egress_pack: frame k starts at o_k = the sum
+ *                       over j < k of (len_j + 15) & ~15, d_desc[k] = UPE_DESC(o_k, len_k) (a bad
+ *                       handle: UPE_DESC(16, 0)), the frame's bytes are followed by zeros up to
+ *                       the next 16-byte boundary.  Frame k is written only if
+ *                       o_k + ((len_k + 15) & ~15) <= out_bytes; offsets ascend, so the written
+ *                       frames are a prefix, counted in `packed`, and `need` is the size to retry
+ *                       with.  d_desc and d_timestamp entries from `packed` on, d_ctrl entries
+ *                       naming a position from `packed` on, and anything at or beyond
+ *                       d_out + out_bytes are not written.  The UPE_FRAME_TAIL bytes after the
+ *                       last frame are the caller's to provide, as for upe_gpu_egress_pack.  The
+ *                       only mode whose output upe_gpu_process_segmented and upe_gpu_egress_pack
+ *                       accept.
+ * In REF and WINDOW mode packed = n.
+ *
+ * Side outputs.  d_timestamp[k] (optional) = buffer s_k's timestamp, not interpreted.
+ * d_ctrl[0 .. n_ctrl) (optional) = the positions k, ascending, of the packets for which
+ * handle_control_packet may write a neighbour table (reference src/worker.c:23-104; the rule of
+ * upe_gpu_process_segmented's marking pass and of upe_gpu_worker_run): ethertype 0x0806 with
+ * bytes 14..19 equal to 00 01 08 00 06 04, or ethertype 0x86DD with len >= 78, byte 20 equal to
+ * 58 and byte 54 135 or 136; bytes at or past len read as zero.  Those are where a caller cuts
+ * the batch.  bad, first_bad, n_ctrl and first_ctrl count all n handles in every mode, whether or
+ * not d_ctrl is given.
+ *
+ * Frames are read in whole 16-byte quads (the quad holding a frame's last byte is read whole,
+ * never a quad past it).  Asynchronous on `stream` (at most three launches; scratch lives in the
+ * context, so a context's gathers are queued one after another).  n == 0 zeroes *d_info with
+ * first_bad = first_ctrl = UINT64_MAX and launches nothing.  -1 before any launch: a NULL
+ * context; a NULL required pointer with n > 0 (d_info always); an unknown mode; stride or
+ * pool_bytes outside the rules above, or a pool that is not 16-byte aligned; d_out not 16-byte
+ * aligned, given in REF mode or missing in the other modes; out_bytes below n * UPE_HDR_WINDOW
+ * in WINDOW mode; n beyond the kernels' 32-bit indexes; a pool that is neither device memory nor
+ * pinned, mapped host memory; d_out overlapping the pool in address — a pool in device memory
+ * counts up to the end of the allocation that holds it, as d_frames does for
+ * upe_gpu_egress_pack.
+ * UPE_INGRESS_BLOCK: packets per workgroup of the gather kernels (batch sizes around it are
+ * where tests look). */
+
+/* Mirrors pktbuf_t, reference include/pktbuf.h:8-14 (2064 bytes). */
+#define UPE_PKTBUF_DATA 2048
+typedef struct {
+    uint64_t timestamp;
+    uint64_t len;
+    uint8_t data[UPE_PKTBUF_DATA];
+} upe_pktbuf_t;
+
+#define UPE_INGRESS_BLOCK 1024
+enum { UPE_INGRESS_REF = 0, UPE_INGRESS_WINDOW = 1, UPE_INGRESS_FULL = 2 };
+
+typedef struct {
+    uint64_t packets;    /* n */
+    uint64_t packed;     /* FULL: frames written (a prefix in handle order); else n */
+    uint64_t bytes;      /* bytes of d_out defined by the call (REF: 0) */
+    uint64_t need;       /* bytes all n would use (== bytes when everything fitted) */
+    uint64_t bad;        /* handles refused */
+    uint64_t first_bad;  /* position k of the first, or UINT64_MAX */
+    uint64_t n_ctrl;     /* packets that may write a neighbour table */
+    uint64_t first_ctrl; /* position of the first, or UINT64_MAX */
+} upe_ingress_info_t;
+
+int upe_gpu_ingress_gather(upe_gpu_ctx_t *ctx, const uint8_t *pool, size_t pool_bytes,
+                           size_t stride,
+                           const uint32_t *d_slot, size_t n, /* buffer indexes, arrival order */
+                           int mode,
+                           uint8_t *d_out, size_t out_bytes, /* NULL / 0 in REF mode */
+                           uint64_t *d_desc,                 /* n */
+                           uint64_t *d_timestamp,            /* n, optional */
+                           uint32_t *d_ctrl,                 /* n, optional */
+                           upe_ingress_info_t *d_info,       /* device, 64 bytes */
+                           void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* RX dispatch: spreading a batch over the worker rings                                        */
 /* ------------------------------------------------------------------------------------------ */
 /* The RX thread's ring choice (reference src/rx_pcap.c:19-25,67-80) for a batch resident in GPU
@@ -818,5 +919,9 @@ UPE_STATIC_ASSERT(sizeof(upe_rule_stat_t) == 16, "rule_stat_t layout");
 UPE_STATIC_ASSERT(sizeof(upe_hdr_rec_t) == 16, "upe_hdr_rec_t layout");
 UPE_STATIC_ASSERT(sizeof(upe_launch_info_t) == 24, "upe_launch_info_t layout");
 UPE_STATIC_ASSERT(sizeof(upe_egress_info_t) == 32, "upe_egress_info_t layout");
+UPE_STATIC_ASSERT(sizeof(upe_pktbuf_t) == 2064, "pktbuf_t layout");
+UPE_STATIC_ASSERT(offsetof(upe_pktbuf_t, len) == 8, "pktbuf_t.len");
+UPE_STATIC_ASSERT(offsetof(upe_pktbuf_t, data) == 16, "pktbuf_t.data");
+UPE_STATIC_ASSERT(sizeof(upe_ingress_info_t) == 64, "upe_ingress_info_t layout");
 
 #endif /* UPE_GPU_H */

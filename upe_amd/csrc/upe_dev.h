@@ -179,6 +179,20 @@ static inline uint32_t mac_lo(const uint8_t* m) {
 static inline uint32_t mac_hi(const uint8_t* m) { return (uint32_t)m[4] | ((uint32_t)m[5] << 8); }
 static inline uint32_t le32(const uint8_t* p) { return mac_lo(p); }
 
+// May handle_control_packet (reference src/worker.c:23-104) call arp_update or ndp_update for
+// this frame?  ARP with the Ethernet/IPv4 header (the learn does not look at len), or an IPv6
+// NS/NA of at least 78 bytes (whether an option carries the address is decided on the host).
+// at(k) is frame byte k, zero at or past len (a zero-filled pktbuf); only k in 12..20 and 54 is
+// asked for.  The same rule as is_table_write in upe_worker.c.
+template <class At>
+UPE_HD UPE_INLINE bool ctrl_table_write(uint32_t len, At at) {
+    const uint32_t et = at(12u) << 8 | at(13u);
+    if (et == 0x0806u)
+        return at(14u) == 0u && at(15u) == 1u && at(16u) == 8u && at(17u) == 0u && at(18u) == 6u &&
+               at(19u) == 4u;
+    return et == 0x86DDu && len >= 78u && at(20u) == 58u && (at(54u) == 135u || at(54u) == 136u);
+}
+
 }  // namespace upe
 
 #endif  // UPE_DEV_H

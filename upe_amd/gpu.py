@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from .layout import (ARP_DTYPE, BATCH_INFO_DTYPE, COUNTERS_DTYPE, FLOW_KEY_DTYPE, L1_DTYPE,
-                     EGRESS_INFO_DTYPE, LAUNCH_INFO_DTYPE, NDP_DTYPE, RULE_DTYPE, RULE_INDEX_INFO_DTYPE,
+                     EGRESS_INFO_DTYPE, INGRESS_INFO_DTYPE, LAUNCH_INFO_DTYPE, NDP_DTYPE, RULE_DTYPE, RULE_INDEX_INFO_DTYPE,
                      RULE_STAT_DTYPE)
 
 LIB_PATH = os.environ.get("UPE_GPU_LIB_DIAG") or os.path.join(
@@ -41,6 +41,10 @@ RX_BLOCK = 1024           # UPE_RX_BLOCK: packets per workgroup of the dispatch 
 
 # upe_gpu_egress_pack (include/upe_gpu.h)
 EGRESS_BLOCK = 1024       # UPE_EGRESS_BLOCK: packets per workgroup of the pack kernels
+
+# upe_gpu_ingress_gather (include/upe_gpu.h)
+INGRESS_BLOCK = 1024      # UPE_INGRESS_BLOCK: packets per workgroup of the gather kernels
+INGRESS_REF, INGRESS_WINDOW, INGRESS_FULL = 0, 1, 2   # UPE_INGRESS_REF / _WINDOW / _FULL
 
 
 # upe_tx_batch_fn: int (*)(void *user, const uint8_t *const *frames, const size_t *lens, int count)
@@ -133,6 +137,7 @@ def _load() -> ctypes.CDLL:
                                     P]),
         "upe_gpu_egress_pack": (I, [P, P, P, P, P, SZ, P, SZ, P, P, P, P]),
         "upe_tx_flush_packed": (I, [P, P, P, SZ, SZ, TX_BATCH_FN, P, P, P]),
+        "upe_gpu_ingress_gather": (I, [P, P, SZ, SZ, P, SZ, I, P, SZ, P, P, P, P, P]),
         "upe_gpu_process_segmented": (I, [P, P, P, P, SZ, P, SZ, P, SZ, ctypes.c_int64, P, P]),
         "upe_gpu_process_emit": (I, [P, P, P, P, P, SZ, P]),
         "upe_gpu_process_emit_tx": (I, [P, P, P, P, P, P, P, SZ, P]),
@@ -195,7 +200,7 @@ EXPORTED = ("upe_gpu_last_error", "upe_gpu_device_count", "upe_gpu_local_cpus", 
             "upe_tx_flush", "upe_tx_flush_groups", "upe_gpu_process_emit_tx", "upe_gpu_hdr_layout",
             "upe_rules_compile", "upe_gpu_reload_image", "upe_rules_image_free",
             "upe_gpu_worker_run", "upe_gpu_rx_dispatch", "upe_gpu_egress_pack",
-            "upe_tx_flush_packed")
+            "upe_tx_flush_packed", "upe_gpu_ingress_gather")
 
 
 def _check(rc: int, what: str) -> None:
@@ -470,6 +475,30 @@ class GpuWorker:
     def fetch_egress_info(self, info) -> np.ndarray:
         """The upe_egress_info_t a pack wrote to the device (synchronises)."""
         x = np.zeros(1, EGRESS_INFO_DTYPE)
+        self.sync()
+        self.d2h(x, info)
+        self.sync()
+        return x[0]
+
+    def ingress_gather(self, pool, pool_bytes: int, stride: int, slot, n: int, mode: int, desc,
+                       info, out=None, out_bytes: int = 0, timestamp=None, ctrl=None,
+                       stream=None) -> None:
+        """upe_gpu_ingress_gather: a burst of pktbuf handles (slot: n uint32 buffer indexes into
+        the pool of stride-byte buffers) gathered into a device batch (ingress.gather_host is the
+        same on the host).  pool: device memory, or pinned host memory (its address as an int).
+        Device buffers: desc (n uint64), info (64 bytes, INGRESS_INFO_DTYPE), out (out_bytes,
+        16-byte aligned; None in INGRESS_REF mode), optional timestamp (n uint64) and ctrl (n
+        uint32)."""
+        _check(LIB.upe_gpu_ingress_gather(self._ctx, _dev_ptr(pool) or None, pool_bytes, stride,
+                                          _dev_ptr(slot) or None, n, mode, _dev_ptr(out) or None,
+                                          out_bytes, _dev_ptr(desc) or None,
+                                          _dev_ptr(timestamp) or None, _dev_ptr(ctrl) or None,
+                                          _dev_ptr(info) or None, stream or None),
+               "upe_gpu_ingress_gather")
+
+    def fetch_ingress_info(self, info) -> np.ndarray:
+        """The upe_ingress_info_t a gather wrote to the device (synchronises)."""
+        x = np.zeros(1, INGRESS_INFO_DTYPE)
         self.sync()
         self.d2h(x, info)
         self.sync()

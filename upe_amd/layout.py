@@ -63,6 +63,14 @@ LAUNCH_INFO_DTYPE = np.dtype({"names": ["variant", "grid", "deferred", "launches
 EGRESS_INFO_DTYPE = np.dtype([("frames", "<u8"), ("packed", "<u8"), ("bytes", "<u8"),
                               ("need", "<u8")])
 
+# upe_ingress_info_t (include/upe_gpu.h)
+INGRESS_INFO_DTYPE = np.dtype([("packets", "<u8"), ("packed", "<u8"), ("bytes", "<u8"),
+                               ("need", "<u8"), ("bad", "<u8"), ("first_bad", "<u8"),
+                               ("n_ctrl", "<u8"), ("first_ctrl", "<u8")])
+# pktbuf_t (reference include/pktbuf.h:8-14; upe_pktbuf_t, 2064 bytes)
+PKTBUF_DATA = 2048
+PKTBUF_DTYPE = np.dtype([("timestamp", "<u8"), ("len", "<u8"), ("data", "u1", (PKTBUF_DATA,))])
+
 # flow_key_t (reference include/parser.h:134-141; upe_flow_key_t, 44 bytes)
 FLOW_KEY_DTYPE = np.dtype({"names": ["ip_ver", "src_ip", "dst_ip", "src_port", "dst_port",
                                      "protocol"],
