@@ -332,7 +332,9 @@ int upe_gpu_process_emit(upe_gpu_ctx_t *ctx, uint8_t *d_frames, const uint64_t *
  * rule_stats, the L1 state, every verdict code and every record equal those of `count`
  * back-to-back upe_gpu_process_emit() calls over the batches (record slots are counted from the
  * ring's first packet; n is a multiple of 64, so each batch's records stay in its own range);
- * UPE_VF_L1_INIT is relative to the ring's start.  n a multiple of 1024, n * count <= 2^24.  d_done_ns (optional, device or
+ * UPE_VF_L1_INIT is relative to the ring's start.  n a multiple of 1024, n * count <= 2^24 (on a device or
+ * partition of fewer than 256 CUs, with a table of up to 4092 rules: <= 65536 * CUs, the most one
+ * launch takes there).  d_done_ns (optional, device or
  * host-mapped, count entries): for each batch, the time (ns) from the launch's first workgroup
  * to the moment its last workgroup had issued the batch's last stores — per-batch completion
  * latency — or 0 where not stamped (stamps need a linear-scan table, batches of at least

@@ -2,7 +2,8 @@
 // plan-check` builds this file under the host sanitizers (-fsanitize=address,undefined) and runs
 // it.  The expected values are worked out by hand from the planning rules at the default UPE_*
 // settings: which upe_classify variant a launch asks for, its dynamic LDS region by region, the
-// tiling and grid, the ring stamps and the rule_stats group-by's shape.
+// tiling and grid, the ring stamps, the rule_stats group-by's shape, and the widths the accounting
+// relies on (a group-by chunk's 24-bit packet count, a workgroup's 32-bit byte bins).
 #include <stdio.h>
 
 #include <set>
@@ -155,6 +156,45 @@ static void group_by() {
     CHECK(plan_group_by(0, 5000).nrules == 1);
 }
 
+// The widths the accounting relies on, over the table and batch sizes the accounting tests run
+// (tests/accounting_cases.py) and the largest an API call can bring.
+static void group_by_widths() {
+    const uint32_t small_last = (uint32_t)kSmallRules - (uint32_t)kUnroll;        // pad = kSmallRules
+    const uint32_t lds_last = (uint32_t)kLdsStatsMax - (uint32_t)kUnroll;         // pad = kLdsStatsMax
+    const uint32_t tables[] = {8, small_last, small_last + 1, 1000, lds_last, lds_last + 1,
+                               kHistRange, kHistRange + 1, 65536, 65537, kTssMaxRules};
+    const size_t sizes[] = {1, 63, 64, 65, kHistChunkMin - 1, kHistChunkMin, kHistChunkMin + 1,
+                            kHistChunkMin + 15, 2 * kHistChunkMin + 1, 40005, (size_t)1 << 24,
+                            (size_t)1 << 31, ((size_t)1 << 32) - kTile - 1};
+    for (uint32_t nrules : tables)
+        for (size_t n : sizes) {
+            const GroupByPlan g = plan_group_by(nrules, n);
+            CHECK((size_t)g.grid_x * g.chunk >= n);
+            CHECK((size_t)g.nr * g.range >= nrules && g.range <= kHistRange);
+            CHECK(g.chunk % 8192 == 0);
+            CHECK(g.chunk < (1u << 24));   // a chunk's packets on one rule fit the 24-bit field
+        }
+    // the group-by never sees more than one launch, and a launch is at most 2^24 packets
+    CHECK(kMaxLaunch <= (size_t)1 << 24 && launch_limit(false, 1) == kMaxLaunch);
+    CHECK(kHistChunk < kMaxLaunch);
+    // the classify kernel's LDS bins: no workgroup of any grid gets more than kWgPackets packets
+    // of a launch within its limit, so its bytes on one rule stay below 2^32
+    CHECK(launch_limit(true, 256) == kMaxLaunch && launch_limit(true, 8) == 8 * kWgPackets);
+    CHECK(launch_limit(true, 0) == kWgPackets);
+    for (uint32_t floor : {1u, 2u, 8u, 60u, 255u, 256u, 304u}) {
+        const size_t lim = launch_limit(true, floor);
+        for (uint32_t cap : {floor, 2 * floor, 8 * floor})   // the launch's grid_cap is never below
+            for (size_t n : {(size_t)1, (size_t)65, (size_t)kTile + 1, lim / 2 + 1, lim - 1, lim}) {
+                const Tiling t = plan_tiling(n, cap);
+                CHECK(t.grid <= cap && (size_t)t.ntiles * t.tw * 64 >= n);
+                CHECK(wg_packets(t) <= kWgPackets);
+                CHECK((uint64_t)wg_packets(t) * 65535u < (1ull << 32));
+            }
+    }
+    // one packet more on the smallest grid would not fit
+    CHECK(wg_packets(plan_tiling(launch_limit(true, 8) + 1, 8)) > kWgPackets);
+}
+
 static void variants() {
     int built = 0;
     std::set<uint32_t> words;
@@ -179,6 +219,7 @@ int main() {
     tuple_space();
     ring_stamps();
     group_by();
+    group_by_widths();
     variants();
     if (g_bad) return fprintf(stderr, "plan_check: %d checks failed\n", g_bad), 1;
     printf("plan_check: the launch plan agrees with the hand-derived cases\n");

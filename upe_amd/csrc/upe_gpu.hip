@@ -1912,8 +1912,10 @@ __global__ void __launch_bounds__(kBlock, kWavesPerSimd) upe_classify(Args a) {
 
         // ---- rule_stats: LDS histogram (same-address lanes serialise in the LDS atomic unit,
         // cheaper than a cross-lane reduction per distinct rule).  One 64-bit atomic per packet:
-        // the bin's low word counts packets, the high word bytes; neither carries into the other
-        // (a workgroup's packets and bytes each fit 32 bits, as the u32 views below assume) ----
+        // the bin's low word counts packets, the high word bytes; neither carries into the other:
+        // the host gives no workgroup more than kWgPackets packets (launch_limit and plan_tiling,
+        // upe_plan.h; a batch past that runs as several launches), so a workgroup's packets and
+        // bytes each fit 32 bits, as the u32 views of the flushes below assume ----
         if (lds_stats && ok && ri != kNone)
             atomicAdd(reinterpret_cast<unsigned long long*>(&lds_hist[2 * rsi]),
                       ((unsigned long long)len << 32) | 1ull);
@@ -2086,7 +2088,8 @@ __global__ void __launch_bounds__(kBlock, kWavesPerSimd) upe_classify(Args a) {
 // rule_stats of large tables (more rules than an LDS histogram holds): a group-by of the
 // batch's verdict words by matched rule.  Workgroup (x, y) counts the packets of chunk x whose
 // rule falls in range y in LDS bins (packets << 40 | bytes, which cannot overflow: a chunk holds
-// at most 2^24 packets of at most 65535 bytes), then writes the bins densely into per-chunk
+// at most kHistChunk = 2^23 packets, under the 2^24 the packets field counts to, of at most 65535
+// bytes, under 2^40 in all), then writes the bins densely into per-chunk
 // partials that upe_hist_reduce sums (device atomics per nonzero bin, measured in round 2, were
 // no faster and needed a packed staging array).  Every range re-reads its chunk (for tables of up
 // to 64k rules the 4-byte key the classify pass left — rule << 16 | length, round 4: 6 -> 4 bytes
@@ -2537,6 +2540,7 @@ struct upe_gpu_ctx {
     hipStream_t stream = nullptr;
     int cus = 256;
     int blocks_per_cu_override = 0;   // UPE_GPU_BLOCKS_PER_CU (diagnostic)
+    uint32_t grid_cap = 0;            // UPE_GPU_GRID_CAP (diagnostic): 0 = none
     bool host_tag = false;   // launches on behalf of a host-side loop (upe_gpu_tag_host)
     bool tree_stage = true;  // stage a decision tree's image in LDS when it fits (UPE_GPU_TREE_LDS)
     uint32_t port_mac_lo = 0, port_mac_hi = 0, port_ip4 = 0;
@@ -2830,6 +2834,7 @@ uint32_t resident_grid(upe_gpu_ctx* c, Variant var, size_t lds, hipStream_t s) {
         }
     }
     if (grid > c->paycap) grid = c->paycap;
+    if (c->grid_cap && grid > c->grid_cap) grid = c->grid_cap;   // diagnostic: only ever lowers
     c->resident[key] = grid;
     if (getenv("UPE_GPU_VERBOSE"))
         fprintf(stderr, "upe_gpu: persistent grid %u (occupancy API %d per CU, lds %zu, kernel "
@@ -2962,6 +2967,9 @@ upe_gpu_ctx_t* upe_gpu_open(int device, size_t rule_capacity) {
                 hipSuccess && cus > 0)
             c->cus = cus;
         if (const char* v = getenv("UPE_GPU_BLOCKS_PER_CU")) c->blocks_per_cu_override = atoi(v);
+        // diagnostic: at most this many workgroups in a persistent grid (a small partition's grid
+        // on a whole device); 0 or unset: no cap
+        if (const char* v = getenv("UPE_GPU_GRID_CAP")) c->grid_cap = (uint32_t)strtoul(v, nullptr, 10);
         // diagnostics: the look-back wait before deferring (0 = defer whenever a flag is not yet
         // published), a synchronous agreement report per launch (the switch to the kernel without
         // look-back then happens at a deterministic launch), no kernel without look-back
@@ -3280,11 +3288,15 @@ int upe_gpu_get_l1(upe_gpu_ctx_t* c, upe_l1_state_t* l1) {
 
 namespace {
 // One batch: the classify launch (in place, or emit mode when d_hdr is given), plus the
-// rule_stats group-by for tables over kLdsStatsMax rules.  A launch takes at most kMaxLaunch
-// packets (the kernel's per-lane counters are 16-bit halves; a lane sees at most one packet
-// per tile).
-constexpr size_t kMaxLaunch = (size_t)1 << 24;
-static_assert(kMaxLaunch % 64 == 0, "a split launch starts on a 64-packet group (egress list)");
+// rule_stats group-by for tables over kLdsStatsMax rules.  A launch takes at most
+// launch_limit() packets (upe_plan.h: kMaxLaunch, and fewer where a small grid's workgroups would
+// otherwise outgrow their 32-bit rule_stats bins).
+// The smallest persistent grid resident_grid can answer with: whole workgroups per CU, at least
+// one, unless the diagnostic cap is lower.
+uint32_t min_grid(const upe_gpu_ctx* c) {
+    const uint32_t cus = (uint32_t)c->cus;
+    return c->grid_cap && c->grid_cap < cus ? c->grid_cap : cus;
+}
 // A ring launch's completion stamps (upe_gpu_process_ring_emit): batches of `per` packets.
 struct RingReq {
     size_t per;
@@ -3457,15 +3469,17 @@ int process_impl(upe_gpu_ctx_t* c, const ProcessReq& q) {
     if (n && (!q.frames || !q.desc || !q.verdict)) return fail("null batch buffer");
     if (((uintptr_t)q.frames & 15u) != 0) return fail("frames buffer must be 16-byte aligned");
     if (((uintptr_t)q.hdr & 15u) != 0) return fail("header records must be 16-byte aligned");
-    if (q.ring && n > kMaxLaunch) return fail("a ring holds at most 2^24 packets");
-    // 2. consecutive launches of at most kMaxLaunch packets: the worker's stream semantics are
+    // 2. consecutive launches of at most `limit` packets: the worker's stream semantics are
     // those of one batch (batch_info describes the last launch)
-    if (n > kMaxLaunch) {
-        for (size_t s0 = 0; s0 < n; s0 += kMaxLaunch) {
+    const size_t limit = launch_limit(c->table.nrules_pad <= (uint32_t)kLdsStatsMax, min_grid(c));
+    if (q.ring && n > limit)
+        return fail("a ring holds at most " + std::to_string(limit) + " packets");
+    if (n > limit) {
+        for (size_t s0 = 0; s0 < n; s0 += limit) {
             ProcessReq part = q;
             part.desc += s0;
             part.verdict += s0;
-            part.n = n - s0 < kMaxLaunch ? n - s0 : kMaxLaunch;
+            part.n = n - s0 < limit ? n - s0 : limit;
             if (q.hdr) part.hdr += s0;
             if (q.flow_hash) part.flow_hash += s0;
             part.host = host;
@@ -3587,6 +3601,7 @@ int upe_gpu_process_ring_emit(upe_gpu_ctx_t* c, uint8_t* d_frames, const uint64_
     if (!d_hdr) return fail("null header records");
     if (n % 1024 != 0) return fail("a ring batch must hold a multiple of 1024 packets");
     if (n * count > kMaxLaunch) return fail("a ring holds at most 2^24 packets");
+    // (process_impl refuses a ring past launch_limit(): a ring is one launch)
     const RingReq r{n, reinterpret_cast<unsigned long long*>(d_done_ns)};
     ProcessReq q{d_frames, d_desc, d_verdict, n * count, stream};
     q.hdr = d_hdr;

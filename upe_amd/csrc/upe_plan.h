@@ -51,8 +51,14 @@ constexpr bool kFamLds = UPE_FAM_LDS;
 #define UPE_HIST_RANGE 16384
 #endif
 constexpr uint32_t kHistRange = UPE_HIST_RANGE;   // most rules per workgroup: 128 KB of LDS
-constexpr uint32_t kHistChunk = 1u << 24;   // most packets per workgroup
+// most packets per workgroup: below 2^24, so that a chunk's packets on one rule fit the 24-bit
+// field of a bin (packets << 40 | bytes) and their bytes (65535 each at most) its 40-bit field
+constexpr uint32_t kHistChunk = 1u << 23;
 constexpr uint32_t kHistChunkMin = 8192;
+static_assert(kHistChunk < (1u << 24) && (uint64_t)kHistChunk * 65535u < (1ull << 40),
+              "a group-by bin holds a whole chunk on one rule");
+static_assert(kHistChunk % kHistChunkMin == 0 && kHistChunkMin % 8192 == 0,
+              "chunks start at multiples of 8192");
 #ifndef UPE_HIST_TARGET
 #define UPE_HIST_TARGET 256
 #endif
@@ -193,6 +199,39 @@ inline Tiling plan_tiling(size_t n, uint32_t grid_cap) {
     t.ntiles = (nchunks + t.tw - 1) / t.tw;
     t.grid = t.ntiles == 0 ? 1u : t.ntiles < grid_cap ? t.ntiles : grid_cap;
     return t;
+}
+
+// ---- launch size ------------------------------------------------------------------------------
+// A launch takes at most kMaxLaunch packets; a larger batch runs as consecutive launches.  The
+// bound dates from per-lane counters kept as 16-bit halves (a lane sees at most one packet per
+// tile).  upe_classify has no per-lane counters any more: a wave's ballots go into the workgroup's
+// 32-bit LDS totals (s_tot), which hold any launch's packets, so that reason no longer applies to
+// tables without LDS rule_stats bins (launch_limit below answers kMaxLaunch for them on any grid).
+// The bound stays because the group-by is planned and checked for at most that many packets
+// (plan_group_by, tools/plan_check.cpp), the deferred look-back list packs a packet index into 31
+// bits, and no test runs a longer launch.
+constexpr size_t kMaxLaunch = (size_t)1 << 24;
+static_assert(kMaxLaunch % 64 == 0, "a split launch starts on a 64-packet group (egress list)");
+static_assert(kMaxLaunch <= (size_t)1 << 24, "the group-by is planned for at most 2^24 packets");
+// Tables whose rule_stats the classify kernel bins in LDS (LdsPlan::lds_stats) count a workgroup's
+// packets and bytes per rule in the two 32-bit halves of one bin.  A workgroup owns the tiles
+// blockIdx, blockIdx + grid, ... (plan_tiling), whatever order its waves claim their chunks in, so
+// it sees at most ceil(ntiles / grid) * tw * 64 packets: with at most kWgPackets of them, of at
+// most 65535 bytes each, neither half can wrap.
+constexpr size_t kWgPackets = 65536;
+static_assert((uint64_t)kWgPackets * 65535u < (1ull << 32), "a workgroup's bytes on one rule fit 32 bits");
+static_assert(kWgPackets % kTile == 0, "whole tiles");
+// The most packets of one launch: min_grid = the smallest persistent grid the context can come to
+// (a launch's grid_cap is never below it), so that plan_tiling gives no workgroup more than
+// kWgPackets packets.  With 256 workgroups or more this is kMaxLaunch.
+inline size_t launch_limit(bool lds_stats, uint32_t min_grid) {
+    if (!lds_stats) return kMaxLaunch;
+    const size_t lim = (size_t)(min_grid ? min_grid : 1u) * kWgPackets;
+    return lim < kMaxLaunch ? lim : kMaxLaunch;
+}
+// The most packets plan_tiling hands one workgroup of the grid.
+inline size_t wg_packets(const Tiling& t) {
+    return (size_t)((t.ntiles + t.grid - 1) / t.grid) * t.tw * 64u;
 }
 
 // ---- ring stamps ------------------------------------------------------------------------------
