@@ -842,7 +842,92 @@ int upe_gpu_get_stats(upe_gpu_ctx_t *ctx, upe_counters_t *counters, upe_rule_sta
                       size_t capacity);
 int upe_gpu_reset_stats(upe_gpu_ctx_t *ctx);
 
-/* Kernel timing.  enable = k > 0: every k-th upe_gpu_process() call (calls k/2, k/2 + k, ...
+/* ------------------------------------------------------------------------------------------ */
+/* Latency histogram: the worker's per-packet dataplane latency                                */
+/* ------------------------------------------------------------------------------------------ */
+/* The fourth output of worker_t the reference's stats thread reads (src/main.c:284-351, the
+ * "Dataplane latency" block): latency_hist, sampled at every exit of process_packet that frees or
+ * queues a buffer (src/worker.c:120-122, 132-134, 148-150, 167-169, 206-208, 235-237, 249-251),
+ * not at the early return for an NDP NS/NA that handle_control_packet consumed
+ * (src/worker.c:111).
+ *
+ * The histogram (mirrors latency_histogram_t, reference include/latency.h:21-40, 96 bytes): eight
+ * buckets with the upper bounds UPE_LATENCY_BOUNDS (ns); a sample goes to the first bucket whose
+ * bound it is strictly below, otherwise to the last one.  upe_latency_init zeroes everything
+ * except min_ns = 1000000, so min_ns never exceeds 1000000 and an empty histogram reports that.
+ *
+ * One sample (src/latency.c:41-59): ns = (uint64_t)((double)cycles / cycles_per_ns) in exact
+ * IEEE-754 double arithmetic — the conversion to double rounds to nearest even, the division is
+ * one correctly rounded division, the conversion back truncates — then buckets[b] += 1,
+ * total_count += 1, sum_ns += ns (modulo 2^64), min_ns and max_ns updated.
+ *
+ * Which packets (the batch forms): packet k is sampled iff timestamps[k] > 0 (src/worker.c:120:
+ * a buffer nobody stamped is not sampled) and the code of verdicts[k] is not UPE_V_CONSUMED;
+ * cycles = now - timestamps[k] as a 64-bit wrapping subtraction.  ARP packets are sampled (they
+ * leave through the parse-fail exit whether or not a reply was sent).  verdicts == NULL: nothing
+ * was consumed.
+ *
+ * `now` is ONE value per call: the caller's TSC reading at the point it considers the batch done.
+ * A batch finishes as a whole, so this is the batch's completion time, not a per-packet instant;
+ * the reference reads the TSC once per packet, at that packet's exit.
+ *
+ * Where the reference is undefined and this library is not.  The reference divides by a
+ * g_cycles_per_ns that defaults to 0.0, and a quotient of 2^64 or more is undefined behaviour in
+ * its cast.  Here a calibration that is not finite and > 0 is refused (-1, nothing changes), and
+ * ns saturates at UINT64_MAX for a quotient of 2^64 or more.  upe_latency_percentile takes a
+ * percentile below 0 (or NaN) as 0 and a target of 2^64 or more as UINT64_MAX.
+ *
+ * upe_latency_percentile and upe_latency_merge follow src/latency.c:61-90: the upper bound of the
+ * first bucket at which the cumulative count reaches (uint64_t)(percentile * total_count), 0 for
+ * an empty histogram; counts and sums added, min and max combined.  The stats thread merges the
+ * per-worker (here: per-context) histograms this way before printing (src/main.c:317-351).
+ *
+ * Host functions (upe_host.c; no GPU; messages in upe_host_last_error()).
+ * upe_latency_record_batch is upe_gpu_latency_record's exact host equivalent. */
+#define UPE_LATENCY_BUCKETS 8
+#define UPE_LATENCY_BOUNDS 100, 500, 1000, 5000, 10000, 50000, 100000, 1000000
+#define UPE_LATENCY_MIN_INIT 1000000
+typedef struct {
+    uint64_t buckets[UPE_LATENCY_BUCKETS];
+    uint64_t total_count;
+    uint64_t min_ns;
+    uint64_t max_ns;
+    uint64_t sum_ns;
+} upe_latency_hist_t;
+
+void upe_latency_init(upe_latency_hist_t *h);
+int upe_latency_record(upe_latency_hist_t *h, uint64_t cycles, double cycles_per_ns);
+uint64_t upe_latency_percentile(const upe_latency_hist_t *h, double percentile);
+void upe_latency_merge(upe_latency_hist_t *dst, const upe_latency_hist_t *src);
+int upe_latency_record_batch(upe_latency_hist_t *h, const uint64_t *timestamps,
+                             const uint32_t *verdicts, /* optional */
+                             size_t n, uint64_t now, double cycles_per_ns);
+
+/* The context's calibration, as worker_set_tsc_calibration (src/worker.c:346) sets the workers' —
+ * here per context.  cycles_per_ns must be finite and > 0: -1 otherwise, and the previous value
+ * stays.  Measuring it is the caller's business (the caller owns its clock). */
+int upe_gpu_set_tsc(upe_gpu_ctx_t *ctx, double cycles_per_ns);
+
+/* Sample a batch on the device into the histogram the context owns there (it accumulates, as the
+ * counters do): d_timestamp (device, n uint64 — upe_gpu_ingress_gather's d_timestamp as it
+ * stands), d_verdict (device, n uint32 as a classify call left them; NULL = nothing consumed),
+ * `now` as above, the calibration last set.  Asynchronous on `stream`; one launch.  The result
+ * does not depend on the order in which the device visits the packets (integer adds, min, max).
+ * n == 0 launches nothing.  -1 before any launch: a NULL context; NULL timestamps with n > 0; n
+ * beyond the kernel's 32-bit indexes; no successful upe_gpu_set_tsc yet.
+ * UPE_LATENCY_BLOCK: packets per workgroup pass of the kernel (batch sizes around it are where
+ * tests look). */
+#define UPE_LATENCY_BLOCK 1024
+int upe_gpu_latency_record(upe_gpu_ctx_t *ctx, const uint64_t *d_timestamp,
+                           const uint32_t *d_verdict, size_t n, uint64_t now, void *stream);
+
+/* The histogram so far (synchronises), and back to the upe_latency_init state.  Nothing else
+ * resets it: upe_gpu_reset_stats, upe_gpu_load_rules, the reloads and upe_gpu_load_neigh leave
+ * it alone, as the reference keeps latency_hist across a SIGHUP. */
+int upe_gpu_get_latency(upe_gpu_ctx_t *ctx, upe_latency_hist_t *out);
+int upe_gpu_reset_latency(upe_gpu_ctx_t *ctx);
+
+/* Kernel timing. enable = k > 0: every k-th upe_gpu_process() call (calls k/2, k/2 + k, ...
  * after enabling: not the first, which starts from an idle queue) records HIP events on its
  * stream around its launches (classify, plus the rule_stats group-by
  * pass of tables over 4096 rules); sampling keeps the events' own queue cost out of a throughput
@@ -925,5 +1010,10 @@ UPE_STATIC_ASSERT(sizeof(upe_pktbuf_t) == 2064, "pktbuf_t layout");
 UPE_STATIC_ASSERT(offsetof(upe_pktbuf_t, len) == 8, "pktbuf_t.len");
 UPE_STATIC_ASSERT(offsetof(upe_pktbuf_t, data) == 16, "pktbuf_t.data");
 UPE_STATIC_ASSERT(sizeof(upe_ingress_info_t) == 64, "upe_ingress_info_t layout");
+UPE_STATIC_ASSERT(sizeof(upe_latency_hist_t) == 96, "latency_histogram_t layout");
+UPE_STATIC_ASSERT(offsetof(upe_latency_hist_t, total_count) == 64, "latency_histogram_t.total_count");
+UPE_STATIC_ASSERT(offsetof(upe_latency_hist_t, min_ns) == 72, "latency_histogram_t.min_ns");
+UPE_STATIC_ASSERT(offsetof(upe_latency_hist_t, max_ns) == 80, "latency_histogram_t.max_ns");
+UPE_STATIC_ASSERT(offsetof(upe_latency_hist_t, sum_ns) == 88, "latency_histogram_t.sum_ns");
 
 #endif /* UPE_GPU_H */

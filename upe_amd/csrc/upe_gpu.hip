@@ -64,6 +64,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cfloat>
 #include <map>
 #include <atomic>
 #include <new>
@@ -81,6 +82,7 @@
 #include "upe_rules.h"
 #include "upe_egress.h"
 #include "upe_ingress.h"
+#include "upe_latency.h"
 #include "upe_rx.h"
 
 using namespace upe;
@@ -2535,6 +2537,20 @@ struct ApplyPool {
     }
 };
 
+// The latency histogram on the device: UPE_LATENCY_REPLICAS copies, each on a 128-byte line of its
+// own (a workgroup adds to copy blockIdx % replicas, so a line sees 1/64 of a launch's atomics);
+// upe_gpu_get_latency merges them.
+constexpr size_t kLatWords = (size_t)UPE_LATENCY_REPLICAS * UPE_LATENCY_REPLICA_WORDS;
+
+int latency_init_image(std::vector<unsigned long long>& img) {
+    upe_latency_hist_t h;
+    upe_latency_init(&h);
+    img.assign(kLatWords, 0);
+    for (size_t r = 0; r < UPE_LATENCY_REPLICAS; ++r)
+        memcpy(&img[r * UPE_LATENCY_REPLICA_WORDS], &h, sizeof h);
+    return 0;
+}
+
 struct upe_gpu_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -2629,6 +2645,10 @@ struct upe_gpu_ctx {
     DevBuf<uint8_t> eg_scratch;           // upe_gpu_egress_pack: the tile table (upe_egress.hip)
     DevBuf<uint8_t> in_scratch;           // upe_gpu_ingress_gather: tile table + meta (upe_ingress.hip)
     DevBuf<unsigned long long> ring_wg;   // ring launches: per-batch counters + time origin
+    // the latency histogram (upe_gpu_latency_record, upe_latency.hip): replicas of the 12 words
+    // of a upe_latency_hist_t, touched by nothing but the four latency calls
+    DevBuf<unsigned long long> lat_hist;
+    double cycles_per_ns = 0.0;           // upe_gpu_set_tsc: 0 until it succeeds once
 };
 
 namespace {
@@ -2997,6 +3017,11 @@ upe_gpu_ctx_t* upe_gpu_open(int device, size_t rule_capacity) {
         c->lb.agree_h = nullptr;
     }
     if (arm_state(c) != 0) return failed();
+    {
+        std::vector<unsigned long long> img;
+        if (latency_init_image(img) != 0 || c->lat_hist.put(img.data(), img.size()) != 0)
+            return failed();
+    }
     if ((e = hipMemsetAsync(c->stats.rule, 0, rule_capacity * 2 * sizeof(unsigned long long),
                             c->stream)) != hipSuccess)
         return bad(e, "hipMemsetAsync");
@@ -4460,6 +4485,95 @@ int upe_gpu_reset_stats(upe_gpu_ctx_t* c) {
                                c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_batch = false;
+    return 0;
+}
+
+// The worker's latency histogram (reference src/worker.c:120-122 ... 249-251 per packet,
+// src/latency.c:41-59); the kernel is upe_latency.hip's.
+int upe_gpu_set_tsc(upe_gpu_ctx_t* c, double cycles_per_ns) {
+    if (!c) return fail("null context");
+    if (!(cycles_per_ns > 0.0 && cycles_per_ns <= DBL_MAX))
+        return fail("cycles_per_ns must be finite and > 0");
+    c->cycles_per_ns = cycles_per_ns;
+    return 0;
+}
+
+static int latency_check(upe_gpu_ctx_t* c, const uint64_t* d_timestamp, size_t n) {
+    if (!c) return fail("null context");
+    if (n && !d_timestamp) return fail("null buffer");
+    if (n > 0xFFFFFFFFull - UPE_LATENCY_BLOCK) return fail("n must fit in 32 bits");
+    if (!(c->cycles_per_ns > 0.0))
+        return fail("no calibration: upe_gpu_set_tsc has not succeeded on this context");
+    return 0;
+}
+
+// at most four workgroups per CU, each striding over the batch; UPE_GPU_GRID_CAP lowers it
+static uint32_t latency_grid(const upe_gpu_ctx_t* c) {
+    const uint32_t g = 4u * (uint32_t)c->cus;
+    return c->grid_cap && c->grid_cap < g ? c->grid_cap : g;
+}
+
+int upe_gpu_latency_record(upe_gpu_ctx_t* c, const uint64_t* d_timestamp,
+                           const uint32_t* d_verdict, size_t n, uint64_t now, void* stream) {
+    if (latency_check(c, d_timestamp, n) != 0) return -1;
+    if (n == 0) return 0;
+    DEV_SCOPE(c->device);
+    HIP_TRY(upe_latency_launch(d_timestamp, d_verdict, (uint32_t)n, now, c->cycles_per_ns,
+                               c->lat_hist.p, latency_grid(c), pick(c, stream)));
+    return 0;
+}
+
+// Diagnostic (tools/latency_time.py; not in the header): one upe_gpu_latency_record of n > 0
+// packets between two HIP events, then a plain hipMemcpyAsync of copy_bytes (device to device) on
+// the same stream between two more: the yardstick for the bytes the call reads.  ms[0] = the
+// launch, ms[1] = the copy.  Synchronous.
+int upe_gpu_latency_record_timed(upe_gpu_ctx_t* c, const uint64_t* d_timestamp,
+                                 const uint32_t* d_verdict, size_t n, uint64_t now,
+                                 const uint8_t* copy_src, uint8_t* copy_dst, size_t copy_bytes,
+                                 void* stream, float* ms) {
+    if (!ms || !copy_src || !copy_dst || n == 0) return fail("no output or an empty batch");
+    if (latency_check(c, d_timestamp, n) != 0) return -1;
+    DEV_SCOPE(c->device);
+    hipStream_t s = pick(c, stream);
+    Events<4> ev;
+    if (ev.create() != 0) return -1;
+    HIP_TRY(hipEventRecord(ev.e[0], s));
+    HIP_TRY(upe_latency_launch(d_timestamp, d_verdict, (uint32_t)n, now, c->cycles_per_ns,
+                               c->lat_hist.p, latency_grid(c), s));
+    HIP_TRY(hipEventRecord(ev.e[1], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipEventRecord(ev.e[2], s));
+    HIP_TRY(hipMemcpyAsync(copy_dst, copy_src, copy_bytes, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipEventRecord(ev.e[3], s));
+    HIP_TRY(hipEventSynchronize(ev.e[3]));
+    if (ev.elapsed(&ms[0], 0, 1) != 0) return -1;
+    return ev.elapsed(&ms[1], 2, 3);
+}
+
+int upe_gpu_get_latency(upe_gpu_ctx_t* c, upe_latency_hist_t* out) {
+    if (!c || !out) return fail("null argument");
+    DEV_SCOPE(c->device);
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<unsigned long long> img(kLatWords);
+    HIP_TRY(hipMemcpy(img.data(), c->lat_hist.p, kLatWords * sizeof(unsigned long long),
+                      hipMemcpyDeviceToHost));
+    upe_latency_init(out);
+    for (size_t r = 0; r < UPE_LATENCY_REPLICAS; ++r) {
+        upe_latency_hist_t h;
+        memcpy(&h, &img[r * UPE_LATENCY_REPLICA_WORDS], sizeof h);
+        upe_latency_merge(out, &h);
+    }
+    return 0;
+}
+
+int upe_gpu_reset_latency(upe_gpu_ctx_t* c) {
+    if (!c) return fail("null context");
+    DEV_SCOPE(c->device);
+    HIP_TRY(hipDeviceSynchronize());   // launches on any stream have added what they add
+    std::vector<unsigned long long> img;
+    latency_init_image(img);
+    HIP_TRY(hipMemcpy(c->lat_hist.p, img.data(), kLatWords * sizeof(unsigned long long),
+                      hipMemcpyHostToDevice));
     return 0;
 }
 

@@ -15,11 +15,14 @@
  *                       dropped (src/rx_pcap.c:53-57), the rest packed at 16-byte aligned offsets.
  *   upe_hdr_apply       an emit-mode record (upe_hdr_rec_t) applied to its frame: the rewrite of
  *                       src/worker.c:162-244 as bytes.
+ *   upe_latency_*       the worker's latency histogram (reference include/latency.h:21-40,
+ *                       src/latency.c:35-90) and the host equivalent of upe_gpu_latency_record.
  */
 #define _GNU_SOURCE
 #include <arpa/inet.h>
 #include <ctype.h>
 #include <errno.h>
+#include <float.h>
 #include <net/if.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -435,3 +438,76 @@ int upe_tx_flush_packed(const uint8_t *h_out, const uint64_t *h_out_desc,
 }
 
 int upe_gpu_hdr_layout(void) { return UPE_HDR_LAYOUT; }
+
+/* ---- latency histogram ------------------------------------------------------------------ */
+
+static const uint64_t k_latency_bounds[UPE_LATENCY_BUCKETS] = {UPE_LATENCY_BOUNDS};
+
+/* finite and > 0 (a NaN fails the first comparison, an infinity the second) */
+static int latency_cpn_ok(double cycles_per_ns) {
+    return cycles_per_ns > 0.0 && cycles_per_ns <= DBL_MAX;
+}
+
+/* (uint64_t)x for x >= 0, saturating where the plain cast is undefined */
+static uint64_t latency_trunc(double x) {
+    return x >= 18446744073709551616.0 ? UINT64_MAX : (uint64_t)x;
+}
+
+static void latency_sample(upe_latency_hist_t *h, uint64_t cycles, double cycles_per_ns) {
+    const uint64_t ns = latency_trunc((double)cycles / cycles_per_ns);
+    int b = 0; /* the first bucket whose bound ns is strictly below, else the last */
+    while (b < UPE_LATENCY_BUCKETS - 1 && ns >= k_latency_bounds[b]) b++;
+    h->buckets[b] += 1;
+    h->total_count += 1;
+    h->sum_ns += ns; /* modulo 2^64 */
+    h->min_ns = ns < h->min_ns ? ns : h->min_ns;
+    h->max_ns = ns > h->max_ns ? ns : h->max_ns;
+}
+
+void upe_latency_init(upe_latency_hist_t *h) {
+    memset(h, 0, sizeof *h);
+    h->min_ns = UPE_LATENCY_MIN_INIT;
+}
+
+int upe_latency_record(upe_latency_hist_t *h, uint64_t cycles, double cycles_per_ns) {
+    if (!h) return host_fail("upe_latency_record: null histogram%.0d%s", 0, "");
+    if (!latency_cpn_ok(cycles_per_ns))
+        return host_fail("upe_latency_record: cycles_per_ns must be finite and > 0%.0d%s", 0, "");
+    latency_sample(h, cycles, cycles_per_ns);
+    return 0;
+}
+
+uint64_t upe_latency_percentile(const upe_latency_hist_t *h, double percentile) {
+    if (h->total_count == 0) return 0;
+    const double want = percentile * (double)h->total_count;
+    const uint64_t target = want > 0.0 ? latency_trunc(want) : 0; /* NaN: 0 */
+    /* the first bucket at which the running count reaches the target, else the last */
+    uint64_t seen = h->buckets[0];
+    int b = 0;
+    while (seen < target && b < UPE_LATENCY_BUCKETS - 1) seen += h->buckets[++b];
+    return k_latency_bounds[b];
+}
+
+void upe_latency_merge(upe_latency_hist_t *dst, const upe_latency_hist_t *src) {
+    for (int i = 0; i < UPE_LATENCY_BUCKETS; i++) dst->buckets[i] += src->buckets[i];
+    dst->total_count += src->total_count;
+    dst->sum_ns += src->sum_ns;
+    if (src->min_ns < dst->min_ns) dst->min_ns = src->min_ns;
+    if (src->max_ns > dst->max_ns) dst->max_ns = src->max_ns;
+}
+
+int upe_latency_record_batch(upe_latency_hist_t *h, const uint64_t *timestamps,
+                             const uint32_t *verdicts, size_t n, uint64_t now,
+                             double cycles_per_ns) {
+    if (!h || (n && !timestamps))
+        return host_fail("upe_latency_record_batch: null argument%.0d%s", 0, "");
+    if (!latency_cpn_ok(cycles_per_ns))
+        return host_fail("upe_latency_record_batch: cycles_per_ns must be finite and > 0%.0d%s", 0,
+                         "");
+    for (size_t k = 0; k < n; k++) {
+        if (timestamps[k] == 0) continue;
+        if (verdicts && UPE_VERDICT_CODE(verdicts[k]) == UPE_V_CONSUMED) continue;
+        latency_sample(h, now - timestamps[k], cycles_per_ns);
+    }
+    return 0;
+}

@@ -46,6 +46,9 @@ EGRESS_BLOCK = 1024       # UPE_EGRESS_BLOCK: packets per workgroup of the pack 
 INGRESS_BLOCK = 1024      # UPE_INGRESS_BLOCK: packets per workgroup of the gather kernels
 INGRESS_REF, INGRESS_WINDOW, INGRESS_FULL = 0, 1, 2   # UPE_INGRESS_REF / _WINDOW / _FULL
 
+# upe_gpu_latency_record (include/upe_gpu.h)
+LATENCY_BLOCK = 1024      # UPE_LATENCY_BLOCK: packets per workgroup pass of the histogram kernel
+
 
 # upe_tx_batch_fn: int (*)(void *user, const uint8_t *const *frames, const size_t *lens, int count)
 TX_BATCH_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p,
@@ -138,6 +141,10 @@ def _load() -> ctypes.CDLL:
         "upe_gpu_egress_pack": (I, [P, P, P, P, P, SZ, P, SZ, P, P, P, P]),
         "upe_tx_flush_packed": (I, [P, P, P, SZ, SZ, TX_BATCH_FN, P, P, P]),
         "upe_gpu_ingress_gather": (I, [P, P, SZ, SZ, P, SZ, I, P, SZ, P, P, P, P, P]),
+        "upe_gpu_set_tsc": (I, [P, ctypes.c_double]),
+        "upe_gpu_latency_record": (I, [P, P, P, SZ, ctypes.c_uint64, P]),
+        "upe_gpu_get_latency": (I, [P, P]),
+        "upe_gpu_reset_latency": (I, [P]),
         "upe_gpu_process_segmented": (I, [P, P, P, P, SZ, P, SZ, P, SZ, ctypes.c_int64, P, P]),
         "upe_gpu_process_emit": (I, [P, P, P, P, P, SZ, P]),
         "upe_gpu_process_emit_tx": (I, [P, P, P, P, P, P, P, SZ, P]),
@@ -165,6 +172,11 @@ def _load() -> ctypes.CDLL:
         "upe_rules_match_host": (I, [P, SZ, P, SZ, P, P]),
         "upe_pcap_read": (I, [ctypes.c_char_p, P, SZ, P, SZ, P]),
         "upe_host_last_error": (ctypes.c_char_p, []),
+        "upe_latency_init": (None, [P]),
+        "upe_latency_record": (I, [P, ctypes.c_uint64, ctypes.c_double]),
+        "upe_latency_percentile": (ctypes.c_uint64, [P, ctypes.c_double]),
+        "upe_latency_merge": (None, [P, P]),
+        "upe_latency_record_batch": (I, [P, P, P, SZ, ctypes.c_uint64, ctypes.c_double]),
     })
     for name, (res, args) in sig.items():
         if os.environ.get("UPE_GPU_LIB_DIAG") and not hasattr(lib, name):
@@ -200,7 +212,10 @@ EXPORTED = ("upe_gpu_last_error", "upe_gpu_device_count", "upe_gpu_local_cpus", 
             "upe_tx_flush", "upe_tx_flush_groups", "upe_gpu_process_emit_tx", "upe_gpu_hdr_layout",
             "upe_rules_compile", "upe_gpu_reload_image", "upe_rules_image_free",
             "upe_gpu_worker_run", "upe_gpu_rx_dispatch", "upe_gpu_egress_pack",
-            "upe_tx_flush_packed", "upe_gpu_ingress_gather")
+            "upe_tx_flush_packed", "upe_gpu_ingress_gather",
+            "upe_latency_init", "upe_latency_record", "upe_latency_percentile",
+            "upe_latency_merge", "upe_latency_record_batch", "upe_gpu_set_tsc",
+            "upe_gpu_latency_record", "upe_gpu_get_latency", "upe_gpu_reset_latency")
 
 
 def _check(rc: int, what: str) -> None:
@@ -504,6 +519,29 @@ class GpuWorker:
         self.sync()
         return x[0]
 
+    # ---- the latency histogram ----
+    def set_tsc(self, cycles_per_ns: float) -> None:
+        """upe_gpu_set_tsc: the context's TSC calibration (finite and > 0)."""
+        _check(LIB.upe_gpu_set_tsc(self._ctx, float(cycles_per_ns)), "upe_gpu_set_tsc")
+
+    def latency_record(self, timestamp, verdict, n: int, now: int, stream=None) -> None:
+        """upe_gpu_latency_record: the batch's samples added to the context's histogram on the
+        device (latency.record_host is the same on the host).  Device buffers: timestamp (n
+        uint64), verdict (n uint32, or None: nothing consumed); now: the batch's completion time
+        in TSC cycles."""
+        _check(LIB.upe_gpu_latency_record(self._ctx, _dev_ptr(timestamp) or None,
+                                          _dev_ptr(verdict) or None, n, now & (2**64 - 1),
+                                          stream or None), "upe_gpu_latency_record")
+
+    def get_latency(self) -> np.ndarray:
+        """upe_gpu_get_latency: the histogram's 12 uint64 words (synchronises)."""
+        h = np.zeros(12, np.uint64)
+        _check(LIB.upe_gpu_get_latency(self._ctx, _np_ptr(h)), "upe_gpu_get_latency")
+        return h
+
+    def reset_latency(self) -> None:
+        _check(LIB.upe_gpu_reset_latency(self._ctx), "upe_gpu_reset_latency")
+
     def sync(self, stream=None) -> None:
         _check(LIB.upe_gpu_sync(self._ctx, stream or None), "upe_gpu_sync")
 
@@ -633,6 +671,51 @@ def pcap_read(path: str):
                          desc.shape[0], _np_ptr(info)) != 0:
         raise UpeGpuError(LIB.upe_host_last_error().decode())
     return frames, desc[: int(info["packets"][0])].copy(), info
+
+
+# ---- the latency histogram on the host (upe_host.c; latency.py is the same in numpy) --------
+
+def _host_check(rc: int) -> None:
+    if rc != 0:
+        raise UpeGpuError(LIB.upe_host_last_error().decode())
+
+
+def latency_init() -> np.ndarray:
+    """upe_latency_init: the 12 uint64 words of an empty upe_latency_hist_t."""
+    h = np.zeros(12, np.uint64)
+    LIB.upe_latency_init(_np_ptr(h))
+    return h
+
+
+def latency_record(hist: np.ndarray, cycles: int, cycles_per_ns: float) -> None:
+    """upe_latency_record: one sample into `hist` (in place)."""
+    assert hist.dtype == np.uint64 and hist.size == 12
+    _host_check(LIB.upe_latency_record(_np_ptr(hist), cycles, float(cycles_per_ns)))
+
+
+def latency_record_batch(hist: np.ndarray, timestamps: np.ndarray, verdicts, now: int,
+                         cycles_per_ns: float) -> None:
+    """upe_latency_record_batch: a batch's samples into `hist` (in place)."""
+    assert hist.dtype == np.uint64 and hist.size == 12
+    ts = np.ascontiguousarray(timestamps, np.uint64)
+    v = None if verdicts is None else np.ascontiguousarray(verdicts, np.uint32)
+    assert v is None or v.size == ts.size
+    _host_check(LIB.upe_latency_record_batch(_np_ptr(hist), _np_ptr(ts) if ts.size else None,
+                                             None if v is None or not v.size else _np_ptr(v),
+                                             ts.size, now & (2**64 - 1), float(cycles_per_ns)))
+
+
+def latency_percentile(hist: np.ndarray, percentile: float) -> int:
+    """upe_latency_percentile."""
+    h = np.ascontiguousarray(hist, np.uint64)
+    return int(LIB.upe_latency_percentile(_np_ptr(h), float(percentile)))
+
+
+def latency_merge(dst: np.ndarray, src: np.ndarray) -> None:
+    """upe_latency_merge: src into dst (in place)."""
+    assert dst.dtype == np.uint64 and dst.size == 12
+    s = np.ascontiguousarray(src, np.uint64)
+    LIB.upe_latency_merge(_np_ptr(dst), _np_ptr(s))
 
 
 class PinnedArray:
