@@ -370,7 +370,10 @@ int upe_gpu_process_host(upe_gpu_ctx_t *ctx, uint8_t *h_frames, size_t frames_by
 
 /* The host round trip in emit mode (chunk 0 = 128k packets): the same pipeline, but only the verdicts and the 16-byte
  * rewritten-header records come back (h_hdr, room for n records in the layout above, counted
- * from the batch's first packet; chunks are whole 64-packet groups; pinned for the full rate: 20 bytes per
+ * from the batch's first packet; chunks are whole 64-packet groups; each chunk's records come back
+ * in one copy of the device array, so every slot of h_hdr[0 .. n) is written, and a slot that holds
+ * no record — "not written" by the kernel in the layout above — comes back with unspecified bytes:
+ * read h_hdr through the verdicts, as for any launch; pinned for the full rate: 20 bytes per
  * packet over the link instead of the frames' rewritten span — the link's two directions share
  * its bandwidth, so fewer bytes back let the frames go in faster).  apply_threads >= 0: the
  * records are applied to h_frames on the host (upe_hdr_apply, answered ARP requests copied back)

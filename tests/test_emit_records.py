@@ -16,18 +16,14 @@ def records_from_reference(frames_in, frames_out, desc, verdict) -> np.ndarray:
     """The record the format defines for each packet, from the reference's output frame."""
     offs = desc_offsets(desc)
     rec = np.zeros((len(offs), 16), np.uint8)
-    for i in np.nonzero((verdict & 0xF) == V_FWD)[0]:
-        o = int(offs[i])
-        out = frames_out[o:o + 26]
-        v6 = frames_in[o + 12] == 0x86 and frames_in[o + 13] == 0xDD
-        rec[i, :12] = out[:12]
-        if v6:
-            rec[i, 12] = out[21]
-            rec[i, 15] = 6
-        else:
-            rec[i, 12] = out[22]
-            rec[i, 13:15] = out[24:26]
-            rec[i, 15] = 4
+    fwd = np.nonzero((verdict & 0xF) == V_FWD)[0]
+    o = offs[fwd]
+    out = frames_out[o[:, None] + np.arange(26)[None, :]]
+    v6 = (frames_in[o + 12] == 0x86) & (frames_in[o + 13] == 0xDD)
+    rec[fwd, :12] = out[:, :12]
+    rec[fwd, 12] = np.where(v6, out[:, 21], out[:, 22])
+    rec[fwd, 13:15] = np.where(v6[:, None], 0, out[:, 24:26])
+    rec[fwd, 15] = np.where(v6, 6, 4)
     return rec
 
 
