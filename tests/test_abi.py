@@ -6,6 +6,7 @@ from __future__ import annotations
 import ctypes
 import os
 import re
+import shutil
 import subprocess
 import tempfile
 
@@ -33,6 +34,34 @@ def test_library_loads_and_exports_every_declared_symbol():
     missing = [s for s in syms if not hasattr(lib, s)]
     assert not missing, f"declared in upe_gpu.h but not exported: {missing}"
     assert sorted(gpu.EXPORTED) == syms
+
+
+# Exported on purpose without a declaration in include/upe_gpu.h: the diagnostics the tools load
+# by name (tools/*_time.py, tools/tree_cost.py) and the worker loop's launch tag.
+DIAGNOSTICS = [
+    "upe_gpu_egress_pack_timed",
+    "upe_gpu_ingress_gather_timed",
+    "upe_gpu_latency_record_timed",
+    "upe_gpu_rx_dispatch_timed",
+    "upe_gpu_tag_host",
+    "upe_tree_profile_host",
+]
+# What the toolchain exports on its own account: weak instantiations of standard-library
+# templates, and the HIP compilation-unit ids (one per .hip unit).
+TOOLCHAIN = re.compile(r"^(_ZNK?St|_ZSt|_ZT[ISV]NSt|__hip_cuid_)")
+
+
+def test_library_exports_nothing_but_the_abi_and_the_diagnostics():
+    """The library's units share the context and a few helpers (csrc/upe_ctx.h, process_impl);
+    none of that is part of the surface, and no diagnostic a tool loads has gone."""
+    from upe_amd import gpu
+
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    out = subprocess.run([nm, "-D", "--defined-only", gpu.LIB_PATH], capture_output=True,
+                         text=True, check=True).stdout
+    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    ours = sorted(n for n in names if not TOOLCHAIN.match(n))
+    assert ours == sorted(declared_symbols() + DIAGNOSTICS)
 
 
 def test_library_is_gfx950_code_object():

@@ -22,8 +22,8 @@
 // Functions one unit of the library defines for another: not exported.
 #define UPE_INTERNAL __attribute__((visibility("hidden")))
 
-// The library's one error slot (upe_gpu.hip; upe_worker.c uses it too): sets the calling thread's
-// upe_gpu_last_error() message and returns -1.
+// The library's one error slot (upe_gpu.hip; every unit and upe_worker.c use it): sets the calling
+// thread's upe_gpu_last_error() message and returns -1.
 extern "C" UPE_INTERNAL int upe_gpu_set_last_error(const char* msg);
 
 namespace upe {

@@ -28,8 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/upe_gpu.h"
-#include "upe_egress.h"
+#include "upe_ctx.h"
 
 namespace {
 
@@ -346,13 +345,14 @@ Tab tab_of(void* scratch, uint32_t T) {
     return t;
 }
 
-}  // namespace
-
+// Bytes of scratch one pack of n packets needs (n > 0).
 size_t upe_egress_scratch_bytes(uint32_t n) {
     const size_t tp = ((size_t)tiles_of(n) + 1u) & ~(size_t)1u;
     return tp * (sizeof(uint64_t) + 3 * sizeof(uint32_t));
 }
 
+// Queue the three passes on `s`, with the arguments as egress_pack has checked them.  hdr NULL:
+// the frames are copied; else each forwarded frame gets its record.
 hipError_t upe_egress_launch(const uint8_t* frames, const uint64_t* desc, const uint32_t* verdict,
                              const upe_hdr_rec_t* hdr, uint32_t n, uint8_t* out,
                              uint64_t out_bytes, uint64_t* out_desc, uint32_t* out_index,
@@ -383,3 +383,79 @@ hipError_t upe_egress_launch(const uint8_t* frames, const uint64_t* desc, const 
     if ((e = hipGetLastError()) != hipSuccess) return e;
     return ev ? hipEventRecord(ev[3], s) : hipSuccess;
 }
+
+using namespace upe;
+
+// The egress batch builder (reference src/worker.c:240-243, 287-303: the frames queued for
+// tx_send_batch, in order).  ev: NULL, or four events recorded before the size pass and after each
+// pass (tools/egress_pack_time.py).
+int egress_pack(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc,
+                const uint32_t* d_verdict, const upe_hdr_rec_t* d_hdr, size_t n, uint8_t* d_out,
+                size_t out_bytes, uint64_t* d_out_desc, uint32_t* d_out_index,
+                upe_egress_info_t* d_info, void* stream, hipEvent_t* ev) {
+    if (!c) return fail("null context");
+    if (!d_info || (n && (!d_frames || !d_desc || !d_verdict || !d_out || !d_out_desc)))
+        return fail("null buffer");
+    if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0 ||
+        (reinterpret_cast<uintptr_t>(d_frames) & 15u) != 0 ||
+        (reinterpret_cast<uintptr_t>(d_hdr) & 15u) != 0)
+        return fail("d_out, d_frames and d_hdr must be 16-byte aligned");
+    if (n > 0xFFFFFFFFull - UPE_EGRESS_BLOCK) return fail("n must fit in 32 bits");
+    DEV_SCOPE(c->device);
+    hipStream_t s = pick(c, stream);
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_info, 0, sizeof(upe_egress_info_t), s));
+        return 0;
+    }
+    // where the frames end is not known here: they count up to the end of their allocation
+    const uintptr_t fr = reinterpret_cast<uintptr_t>(d_frames);
+    const uintptr_t out = reinterpret_cast<uintptr_t>(d_out);
+    const uintptr_t fr_end = alloc_end(d_frames, fr + 1);
+    if (out < fr_end && fr < out + (out_bytes ? out_bytes : 1))
+        return fail("d_out overlaps d_frames");
+    const size_t need = upe_egress_scratch_bytes((uint32_t)n);
+    if (c->eg_scratch.reserve(need, need + need / 4) != 0) return -1;
+    HIP_TRY(upe_egress_launch(d_frames, d_desc, d_verdict, d_hdr, (uint32_t)n, d_out, out_bytes,
+                              d_out_desc, d_out_index, d_info, c->eg_scratch.p, s, ev));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int upe_gpu_egress_pack(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc,
+                        const uint32_t* d_verdict, const upe_hdr_rec_t* d_hdr, size_t n,
+                        uint8_t* d_out, size_t out_bytes, uint64_t* d_out_desc,
+                        uint32_t* d_out_index, upe_egress_info_t* d_info, void* stream) {
+    return egress_pack(c, d_frames, d_desc, d_verdict, d_hdr, n, d_out, out_bytes, d_out_desc,
+                       d_out_index, d_info, stream, nullptr);
+}
+
+// Diagnostic (tools/egress_pack_time.py; not in the header): one pack of n > 0 packets with HIP
+// events around each pass, then a plain device-to-device copy of the packed bytes (info.bytes,
+// d_out -> d_copy, out_bytes of room) on the same stream: the floor of the copy pass.
+// ms[0..3] = the size, scan and copy pass and that copy.  Synchronous.
+int upe_gpu_egress_pack_timed(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc,
+                              const uint32_t* d_verdict, const upe_hdr_rec_t* d_hdr, size_t n,
+                              uint8_t* d_out, size_t out_bytes, uint64_t* d_out_desc,
+                              uint32_t* d_out_index, upe_egress_info_t* d_info, uint8_t* d_copy,
+                              void* stream, float* ms) {
+    if (!c || !ms || !d_copy || n == 0)
+        return fail("null context, no output or an empty batch");
+    DEV_SCOPE(c->device);
+    hipStream_t s = pick(c, stream);
+    Events<6> ev;
+    if (ev.create() != 0 ||
+        egress_pack(c, d_frames, d_desc, d_verdict, d_hdr, n, d_out, out_bytes, d_out_desc,
+                    d_out_index, d_info, stream, ev.e) != 0)
+        return -1;
+    upe_egress_info_t info = {};
+    if (hipMemcpyAsync(&info, d_info, sizeof(info), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return fail("reading the pack's info");
+    return ev.yardstick(d_copy, d_out, info.bytes, hipMemcpyDeviceToDevice, s,
+                        "the device-to-device copy", ms);
+}
+
+}  // extern "C"

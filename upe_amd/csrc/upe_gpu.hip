@@ -1,5 +1,9 @@
-// upe_gpu.hip — MI355X (gfx950 / CDNA4) batch dataplane for UPE's per-packet worker hot path,
-// and the extern "C" ABI declared in include/upe_gpu.h.
+// upe_gpu.hip — MI355X (gfx950 / CDNA4) batch dataplane for UPE's per-packet worker hot path:
+// the classify kernels and the host side that launches them (context create and destroy, the rule
+// and neighbour loads, process_impl, the device-buffer upe_gpu_process* calls, statistics, timing)
+// of the extern "C" ABI declared in include/upe_gpu.h.  The context itself is upe_ctx.h's; the
+// other stages (upe_rx.hip, upe_egress.hip, upe_ingress.hip, upe_latency.hip), the host paths
+// (upe_hostpath.hip) and the segmented path (upe_segment.hip) are units of their own.
 //
 // One lane owns one packet.  Per packet the kernel does what reference process_packet() does
 // (src/worker.c:106-253): control-packet classification (src/worker.c:23-104), the fixed-format
@@ -64,26 +68,15 @@
 
 #include <algorithm>
 #include <array>
-#include <cfloat>
 #include <map>
 #include <atomic>
 #include <new>
 #include <string>
-#include <condition_variable>
-#include <functional>
 #include <memory>
-#include <mutex>
-#include <thread>
 #include <vector>
 
-#include "../../include/upe_gpu.h"
-#include "upe_dev.h"
+#include "upe_ctx.h"
 #include "upe_plan.h"
-#include "upe_rules.h"
-#include "upe_egress.h"
-#include "upe_ingress.h"
-#include "upe_latency.h"
-#include "upe_rx.h"
 
 using namespace upe;
 
@@ -2209,10 +2202,8 @@ __global__ void __launch_bounds__(256) upe_hist_reduce(const unsigned long long*
 // Egress list: the indexes of the packets with a given verdict code, in packet order (the order
 // process_packet queues frames for tx_send_batch, reference src/worker.c:240-243).  Pass 1
 // counts per block; pass 2 gives each block its offset (sum of the counts before it) and writes
-// its indexes with wave ballots.
+// its indexes with wave ballots.  (kCompactBlock packets per workgroup: upe_ctx.h.)
 // ------------------------------------------------------------------------------------------
-constexpr uint32_t kCompactBlock = 4096;   // packets per workgroup (256 threads x 16)
-
 __global__ void __launch_bounds__(256) upe_compact_count(const uint32_t* verdict, uint32_t n,
                                                          uint32_t code, uint32_t* counts) {
     __shared__ uint32_t s_c;
@@ -2268,391 +2259,6 @@ __global__ void __launch_bounds__(256) upe_compact_write(const uint32_t* verdict
 // ------------------------------------------------------------------------------------------
 thread_local std::string g_err;   // upe_gpu_last_error(); fail() sets it (upe_gpu_set_last_error)
 
-#define HIP_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return fail(std::string(#expr) + ": " + hipGetErrorString(e_));                  \
-    } while (0)
-
-// Makes the context's device current for the duration of an ABI call and restores the caller's
-// current device on return (the ABI must not move the calling thread to another device).
-struct DevScope {
-    int prev = -1;
-    hipError_t e;
-    explicit DevScope(int d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        e = prev == d ? hipSuccess : hipSetDevice(d);
-    }
-    ~DevScope() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-    DevScope(const DevScope&) = delete;
-    DevScope& operator=(const DevScope&) = delete;
-};
-#define DEV_SCOPE(dev)                                                                       \
-    DevScope dev_scope_(dev);                                                                \
-    HIP_TRY(dev_scope_.e)
-
-// A device allocation of `cap` elements that its holder owns: freed with it, movable, not
-// copyable.  It converts to the raw pointer, which is what kernels, Args and DevState take.
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
-    DevBuf& operator=(DevBuf&& o) noexcept {
-        if (this != &o) {
-            reset();
-            p = o.p, cap = o.cap;
-            o.p = nullptr, o.cap = 0;
-        }
-        return *this;
-    }
-    ~DevBuf() { reset(); }
-    void reset() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    // Room for `count` elements: when there is not, the old allocation is freed first and one of
-    // `want` elements (>= count: each caller's growth formula) made.  Nothing is kept across a
-    // growth, and after a failed one the buffer holds nothing.
-    int reserve(size_t count, size_t want) {
-        if (count <= cap) return 0;
-        reset();
-        HIP_TRY(hipMalloc(&p, want * sizeof(T)));
-        cap = want;
-        return 0;
-    }
-    // (an empty buffer) `count` elements uploaded from the host; none: stays empty
-    int put(const T* src, size_t count) {
-        if (reserve(count, count) != 0) return -1;
-        if (count) HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
-        return 0;
-    }
-    // (an empty buffer) `count` zeroed elements
-    int zeros(size_t count) {
-        if (reserve(count, count) != 0) return -1;
-        HIP_TRY(hipMemset(p, 0, count * sizeof(T)));
-        return 0;
-    }
-    operator T*() const { return p; }
-    T* operator->() const { return p; }
-};
-
-// The timing events of one diagnostic call, destroyed with it.
-template <int N>
-struct Events {
-    hipEvent_t e[N] = {};
-    Events() = default;
-    Events(const Events&) = delete;
-    Events& operator=(const Events&) = delete;
-    ~Events() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-    int create() {
-        for (hipEvent_t& x : e) HIP_TRY(hipEventCreate(&x));
-        return 0;
-    }
-    int elapsed(float* ms, int from, int to) {
-        HIP_TRY(hipEventElapsedTime(ms, e[from], e[to]));
-        return 0;
-    }
-};
-
-// The neighbour snapshot on the device (NeighIndex): one value, uploaded whole and then swapped
-// into the context (upe_gpu_load_neigh).
-struct NeighTable {
-    DevBuf<uint4> arp, ndp;
-    uint32_t arp_bits = 0, arp_seed = 0, ndp_bits = 0, ndp_seed = 0;
-    // (an empty table)
-    int upload(const NeighImage& im) {
-        if (arp.put(im.arp.data(), im.arp.size()) || ndp.put(im.ndp.data(), im.ndp.size()))
-            return -1;
-        arp_bits = im.arp_bits, arp_seed = im.arp_seed;
-        ndp_bits = im.ndp_bits, ndp_seed = im.ndp_seed;
-        return 0;
-    }
-};
-
-// The compiled rule table on the device (upe_rule_image, upe_rules.h): one value, uploaded whole
-// and then swapped into the context (install_image).
-struct DeviceTable {
-    DevBuf<RuleV4> rv4;
-    DevBuf<RuleV6> rv6;
-    DevBuf<int2> rinfo;
-    DevBuf<uint4> fam;                // FamTable image (linear-scan tables > kSmallRules)
-    uint32_t fam4 = 0, fam6 = 0, fam_all = 0, fam_x1idx = 0;
-    // whether a packet of each family can be forwarded at all under the table: some rule it can
-    // reach first (up to its family's first catch-all) forwards
-    bool fwd4 = true, fwd6 = true;
-    uint32_t nrules = 0, nrules_pad = 0;
-    std::vector<int2> rinfo_host;     // (action, rule_id) per sorted index
-    // tuple-space index of large tables (null when the linear scan is used)
-    DevBuf<TssGroup> tg4, tg6;
-    DevBuf<uint4> tt4, tt6;
-    DevBuf<uint16_t> tfs;             // staged fingerprint image
-    uint32_t nfs = 0;                 // its length in uint4
-    uint32_t ng4 = 0, ng6 = 0;
-    bool tss = false;
-    // decision-tree index over the family lists (null / tree_ok false when not used)
-    DevBuf<uint4> tree;
-    bool tree_ok = false;
-    uint32_t tree_words = 0, tree_loff = 0;
-    upe_rule_index_info_t tree_info = {};
-
-    // (an empty table) every image of `im` on the device
-    int upload(const upe_rule_image& im) {
-        const TreeImage& t = im.t;
-        if (rv4.put(im.v4.data(), im.pad) || rv6.put(im.v6.data(), im.pad) ||
-            rinfo.put(im.info.data(), im.pad) || fam.put(im.fimg.data(), im.fimg.size()) ||
-            (im.tss && (tfs.put(im.fps.data(), im.fps.size()) ||
-                        tg4.put(im.f4.groups.data(), im.f4.groups.size()) ||
-                        tg6.put(im.f6.groups.data(), im.f6.groups.size()) ||
-                        tt4.put(im.f4.slots.data(), im.f4.slots.size()) ||
-                        tt6.put(im.f6.slots.data(), im.f6.slots.size()))) ||
-            (im.tree_ok && tree.put(im.timg.data(), im.timg.size())))
-            return -1;
-        fam4 = im.fam4, fam6 = im.fam6, fam_all = im.fam_all, fam_x1idx = im.fam_x1idx;
-        fwd4 = im.fwd4, fwd6 = im.fwd6;
-        nrules = (uint32_t)im.count;
-        nrules_pad = (uint32_t)im.pad;
-        rinfo_host = im.info;
-        tss = im.tss;
-        nfs = tss ? (uint32_t)(im.fps.size() / 8) : 0u;
-        ng4 = tss ? (uint32_t)im.f4.groups.size() : 0u;
-        ng6 = tss ? (uint32_t)im.f6.groups.size() : 0u;
-        tree_ok = im.tree_ok;
-        tree_words = tree_ok ? (uint32_t)im.timg.size() : 0u;
-        tree_loff = tree_ok ? (uint32_t)(2 * t.nodes.size()) : 0u;
-        if (tree_ok)
-            tree_info = upe_rule_index_info_t{(uint64_t)t.nodes.size(), (uint64_t)t.leaves.size(),
-                                              t.depth[0], t.depth[1], t.max_leaf,
-                                              t.trees[0] | t.trees[1] << 16};
-        return 0;
-    }
-    // The plan's view of the loaded tables (upe_plan.h): this one's, the neighbour indexes' sizes
-    // and whether a tree may be staged in LDS (a context option).
-    TableShape shape(const NeighTable& nb, bool tree_stage) const {
-        return TableShape{tss, nrules, nrules_pad, nb.arp_bits, nb.ndp_bits, nfs,
-                          tree_ok, tree_stage, tree_words, fam4, fam6, fam_all != 0};
-    }
-};
-
-// ------------------------------------------------------------------------------------------
-// Control packets that write a neighbour table (upe_gpu_process_segmented).  A packet is
-// marked when handle_control_packet (reference src/worker.c:23-104) may call arp_update or
-// ndp_update for it: ARP with the Ethernet/IPv4 header (the learn does not look at len), or an
-// IPv6 NS/NA of at least 78 bytes (whether an option carries the address is decided on the
-// host, from the gathered bytes).  Bytes at or past len read as zero (zero-filled pktbuf).
-// Marks are verdict-shaped words (code 1 = marked) so upe_compact_* lists them in order.
-// ------------------------------------------------------------------------------------------
-constexpr uint32_t kCtrlWin = 256;   // bytes of each marked frame gathered for the host
-
-__global__ void __launch_bounds__(256) upe_ctrl_mark(const uint8_t* frames, const uint64_t* desc,
-                                                     uint32_t n, uint32_t* marks) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t d = desc[i];
-    const uint32_t len = (uint32_t)(d & 0xFFFFu);
-    const uint8_t* p = frames + (d >> 16);
-    auto at = [&](uint32_t k) -> uint32_t { return k < len ? (uint32_t)p[k] : 0u; };
-    marks[i] = ctrl_table_write(len, at) ? 1u : 0u;
-}
-
-// One workgroup per marked packet: its first kCtrlWin bytes (zero past len) and its length.
-__global__ void __launch_bounds__(256) upe_ctrl_gather(const uint8_t* frames, const uint64_t* desc,
-                                                       const uint32_t* index, uint8_t* win,
-                                                       uint32_t* lens) {
-    const uint32_t i = index[blockIdx.x];
-    const uint64_t d = desc[i];
-    const uint32_t len = (uint32_t)(d & 0xFFFFu);
-    const uint32_t k = threadIdx.x;
-    win[(size_t)blockIdx.x * kCtrlWin + k] = k < len ? frames[(d >> 16) + k] : (uint8_t)0;
-    if (k == 0) lens[blockIdx.x] = len;
-}
-
-}  // namespace
-
-// A small pool of host threads that run one job over slices: job(slice, slices), the caller
-// being slice 0 (upe_gpu_process_host_emit applies the returned records to the caller's frames
-// with it while later chunks are on the link).  Threads are pinned to the GPU's NUMA-local CPUs.
-struct ApplyPool {
-    std::vector<std::thread> th;
-    std::mutex mu;
-    std::condition_variable go, done;
-    std::function<void(unsigned, unsigned)> job;
-    uint64_t gen = 0;
-    unsigned left = 0;
-    bool stop = false;
-
-    ApplyPool(unsigned n, const std::vector<int>& cpus) {
-        for (unsigned t = 0; t < n; ++t)
-            th.emplace_back([this, t, n, cpus] {
-                if (!cpus.empty()) {   // after the caller's CPU (local slot 0)
-                    cpu_set_t one;
-                    CPU_ZERO(&one);
-                    CPU_SET(cpus[(1 + t) % cpus.size()], &one);
-                    (void)pthread_setaffinity_np(pthread_self(), sizeof one, &one);
-                }
-                uint64_t seen = 0;
-                for (;;) {
-                    std::function<void(unsigned, unsigned)> f;
-                    {
-                        std::unique_lock<std::mutex> lk(mu);
-                        go.wait(lk, [&] { return stop || gen != seen; });
-                        if (stop) return;
-                        seen = gen;
-                        f = job;
-                    }
-                    f(t + 1, n + 1);
-                    std::lock_guard<std::mutex> lk(mu);
-                    if (--left == 0) done.notify_one();
-                }
-            });
-    }
-    ~ApplyPool() {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            stop = true;
-        }
-        go.notify_all();
-        for (auto& t : th) t.join();
-    }
-    void run(const std::function<void(unsigned, unsigned)>& f) {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            job = f;
-            left = (unsigned)th.size();
-            ++gen;
-        }
-        go.notify_all();
-        f(0, (unsigned)th.size() + 1);
-        std::unique_lock<std::mutex> lk(mu);
-        done.wait(lk, [&] { return left == 0; });
-    }
-};
-
-// The latency histogram on the device: UPE_LATENCY_REPLICAS copies, each on a 128-byte line of its
-// own (a workgroup adds to copy blockIdx % replicas, so a line sees 1/64 of a launch's atomics);
-// upe_gpu_get_latency merges them.
-constexpr size_t kLatWords = (size_t)UPE_LATENCY_REPLICAS * UPE_LATENCY_REPLICA_WORDS;
-
-int latency_init_image(std::vector<unsigned long long>& img) {
-    upe_latency_hist_t h;
-    upe_latency_init(&h);
-    img.assign(kLatWords, 0);
-    for (size_t r = 0; r < UPE_LATENCY_REPLICAS; ++r)
-        memcpy(&img[r * UPE_LATENCY_REPLICA_WORDS], &h, sizeof h);
-    return 0;
-}
-
-struct upe_gpu_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int cus = 256;
-    int blocks_per_cu_override = 0;   // UPE_GPU_BLOCKS_PER_CU (diagnostic)
-    uint32_t grid_cap = 0;            // UPE_GPU_GRID_CAP (diagnostic): 0 = none
-    bool host_tag = false;   // launches on behalf of a host-side loop (upe_gpu_tag_host)
-    bool tree_stage = true;  // stage a decision tree's image in LDS when it fits (UPE_GPU_TREE_LDS)
-    uint32_t port_mac_lo = 0, port_mac_hi = 0, port_ip4 = 0;
-    // what the launches classify with: each a value that a load uploads whole and then swaps in
-    DeviceTable table;             // the compiled rule table (install_image)
-    NeighTable neigh;              // the neighbour snapshot (upe_gpu_load_neigh)
-    // rule_stats: they outlive a table (upe_gpu_load_rules credits them by rule_id)
-    struct Stats {
-        size_t cap = 0;                       // rule_stats capacity
-        DevBuf<unsigned long long> rule;      // [cap][2] rule_stats by rule_id
-        DevBuf<unsigned long long> idx;       // [kStatReps][pad][2] totals per sorted index, pad
-                                              // the largest table so far
-        DevBuf<unsigned long long> hist_part; // [chunks][nrules] dense group-by partials
-        DevBuf<uint32_t> gb;                  // group-by keys (u32), or u16 lengths
-    } stats;
-    // state: one DevState allocation (see "Sequential state between batches")
-    DevBuf<DevState> st;
-    DevBuf<TilePay> pay;           // [2][paycap] per-workgroup last-hit payloads, by batch parity
-    uint32_t paycap = 0;           // largest grid
-    // launch bookkeeping
-    uint64_t k = 0;                // launches so far: the next batch is batch k
-    uint32_t last_n = 0;           // the last batch's size (batch_info)
-    int last_var = -1;             // kernel variant of the last classify launch
-    uint32_t last_grid = 0;
-    bool have_batch = false;
-    // every launch and state upload is ordered after the previous one, whatever its stream
-    hipStream_t last_stream = nullptr;
-    hipEvent_t order_ev = nullptr;
-    std::map<uint64_t, uint32_t> resident;   // persistent grid per (lds, variant word) (census)
-    hipEvent_t marks[4] = {};      // worker loop completion marks (upe_gpu_mark)
-    // the look-back between a batch's chunks, and the switch to the kernel without it (kNoLB): the
-    // launches' start-state agreement, written by the device into host-mapped memory, and the
-    // first launch whose report counts
-    struct LookBack {
-        // per-batch scratch, for tiles of kWaves chunks
-        DevBuf<uint32_t> flags;    // a look-back flag per chunk (zeroed at allocation)
-        DevBuf<uint32_t> defer;    // 64 deferred look-back candidates (two words each) per chunk
-        uint32_t spin = 5000;      // look-back wait before deferring (UPE_GPU_LB_SPIN, 100 MHz ticks)
-        bool sync = false;         // UPE_GPU_LB_SYNC=1: wait for each launch's agreement report
-        bool allow_nolb = true;    // UPE_GPU_NOLB=0: never use the kernels without look-back
-        bool no_lb = false;
-        uint64_t reset_k = 0;
-        unsigned long long* agree_h = nullptr;
-        unsigned long long* agree_d = nullptr;
-    } lb;
-    // kernel timing (upe_gpu_timing_*)
-    struct Timing {
-        bool on = false;
-        uint32_t every = 1, calls = 0;   // sample every n-th process() call
-        uint32_t phase = 0;        // samples open at calls c with c % every == phase
-        uint32_t span = 1;         // calls one sample's event pair brackets
-        uint32_t left = 0;         // calls left in the open sample (0: none open)
-        uint64_t launches = 0;     // calls covered by closed samples
-        std::vector<hipEvent_t> ev;    // event pool, 3 per sample
-        size_t ev_used = 0;        // 3 per closed sample: start, after the classify, end
-        std::vector<bool> ev_mid;  // per closed sample: the middle event was recorded
-    } timing;
-    // host round trip (upe_gpu_process_host): copy streams and the device slots
-    struct HostSlot {
-        DevBuf<uint8_t> frames;
-        DevBuf<uint64_t> desc;          // desc, verdict (and hdr, once used) hold as many packets
-        DevBuf<uint32_t> verdict;
-        DevBuf<upe_hdr_rec_t> hdr;      // emit-mode records (upe_gpu_process_host_emit)
-        hipEvent_t in_done = nullptr, k_done = nullptr, out_done = nullptr;
-        bool busy = false;
-        uint64_t lo = 0, wb = 0;   // host byte range the slot's copy-back writes
-    };
-    struct HostPath {
-        hipStream_t s_in = nullptr, s_out = nullptr;
-        HostSlot slots[8];
-        uint32_t nslots = 4;       // slots in use (UPE_GPU_HOST_SLOTS, 2..8)
-        // host threads applying emit-mode records to the caller's frames
-        // (upe_gpu_process_host_emit)
-        std::unique_ptr<struct ApplyPool> pool;
-    } host;
-    // upe_gpu_process_segmented scratch: marks / index per packet, gathered windows per mark
-    struct SegScratch {
-        DevBuf<uint32_t> marks, index;
-        DevBuf<uint64_t> count;
-        DevBuf<uint8_t> win;
-        DevBuf<uint32_t> lens;
-    } seg;
-    // single-use scratch
-    DevBuf<uint32_t> compact_counts;      // upe_gpu_compact: per-block counts
-    DevBuf<uint8_t> rx_scratch;           // upe_gpu_rx_dispatch: the passes' tile table (upe_rx.hip)
-    DevBuf<uint8_t> eg_scratch;           // upe_gpu_egress_pack: the tile table (upe_egress.hip)
-    DevBuf<uint8_t> in_scratch;           // upe_gpu_ingress_gather: tile table + meta (upe_ingress.hip)
-    DevBuf<unsigned long long> ring_wg;   // ring launches: per-batch counters + time origin
-    // the latency histogram (upe_gpu_latency_record, upe_latency.hip): replicas of the 12 words
-    // of a upe_latency_hist_t, touched by nothing but the four latency calls
-    DevBuf<unsigned long long> lat_hist;
-    double cycles_per_ns = 0.0;           // upe_gpu_set_tsc: 0 until it succeeds once
-};
-
-namespace {
-
 NeighIndex arp_index(const upe_gpu_ctx* c) {
     return NeighIndex{c->neigh.arp, c->neigh.arp_bits, c->neigh.arp_seed};
 }
@@ -2684,17 +2290,6 @@ int ensure_scratch(upe_gpu_ctx* c, size_t ntiles) {
             c->lb.defer.reserve(2 * 64 * chunks, 2 * 64 * chunks) != 0 || publish(c) != 0)
             return -1;
     }
-    return 0;
-}
-
-// Order work about to be queued on `s` after everything queued so far on the context's state
-// (the last launch, or a state upload), whatever stream that went to.
-int order_on(upe_gpu_ctx* c, hipStream_t s) {
-    if (c->last_stream && c->last_stream != s) {
-        HIP_TRY(hipEventRecord(c->order_ev, c->last_stream));
-        HIP_TRY(hipStreamWaitEvent(s, c->order_ev, 0));
-    }
-    c->last_stream = s;
     return 0;
 }
 
@@ -2740,9 +2335,6 @@ int arm_state(upe_gpu_ctx* c) {
     c->lb.reset_k = 0;
     return 0;
 }
-
-
-hipStream_t pick(upe_gpu_ctx* c, void* s) { return s ? (hipStream_t)s : c->stream; }
 
 // The built variants (variant_built), listed once; kernel i of the table is kBuilt.v[i]'s.
 struct BuiltList {
@@ -3050,6 +2642,8 @@ void upe_gpu_close(upe_gpu_ctx_t* c) {
     delete c;   // the device buffers go with it (DevBuf), on the context's device
 }
 
+}  // extern "C"
+
 namespace {
 // Credit the sorted-index totals of the current table to rule_stats[rule_id] (device) and clear
 // them: called before upe_gpu_load_rules changes the table, so the counts carry over by rule_id
@@ -3115,11 +2709,7 @@ int read_rule_stats(upe_gpu_ctx* c, upe_rule_stat_t* rule_stats, size_t capacity
     }
     return 0;
 }
-}  // namespace
 
-}  // extern "C"
-
-namespace {
 using StatsBuf = DevBuf<unsigned long long>;
 // upe_gpu_load_rules / upe_gpu_reload_rules[_image] with a compiled image: `fresh` (a zeroed
 // rule_stats of fresh_cap entries) replaces the context's statistics on a reload, the old
@@ -3322,27 +2912,6 @@ uint32_t min_grid(const upe_gpu_ctx* c) {
     const uint32_t cus = (uint32_t)c->cus;
     return c->grid_cap && c->grid_cap < cus ? c->grid_cap : cus;
 }
-// A ring launch's completion stamps (upe_gpu_process_ring_emit): batches of `per` packets.
-struct RingReq {
-    size_t per;
-    unsigned long long* done;   // [count] ns after the first workgroup's start, 0 = not stamped
-};
-// One request to process_impl: a batch in device-visible memory, and what is wanted beside the
-// verdicts.
-struct ProcessReq {
-    uint8_t* frames;
-    const uint64_t* desc;
-    uint32_t* verdict;
-    size_t n;
-    void* stream;
-    upe_hdr_rec_t* hdr = nullptr;    // emit mode: [n] rewritten-header records, frames only read
-    uint32_t* flow_hash = nullptr;   // [n] flow hashes (RSS)
-    const RingReq* ring = nullptr;   // the batch is a ring of batches
-    bool host = false;               // launched for a host path (Path::Host)
-    uint32_t* tx = nullptr;          // the egress list (Path::Tx) and its per-group counts
-    uint32_t* tx_cnt = nullptr;
-    size_t tx_base = 0;              // the launch's first packet in the caller's batch
-};
 
 // Timing sample: an event pair around `span` consecutive calls, opened on every
 // every-th call (samples never overlap).
@@ -3387,6 +2956,14 @@ int settle_no_lb(upe_gpu_ctx* c) {
         ((v & 2) || c->neigh.ndp_bits == 0 || !c->table.fwd6))
         c->lb.no_lb = true;
     return 0;
+}
+
+// The plan's view of the loaded tables (upe_plan.h): the rule table's, the neighbour indexes'
+// sizes and whether a tree may be staged in LDS (a context option).
+TableShape table_shape(const upe_gpu_ctx* c) {
+    const DeviceTable& t = c->table;
+    return TableShape{t.tss, t.nrules, t.nrules_pad, c->neigh.arp_bits, c->neigh.ndp_bits, t.nfs,
+                      t.tree_ok, c->tree_stage, t.tree_words, t.fam4, t.fam6, t.fam_all != 0};
 }
 
 // The kernel's arguments but for the tiling and the ring's (process_impl sets those).
@@ -3485,7 +3062,9 @@ int launch_group_by(upe_gpu_ctx* c, const uint32_t* d_verdict, size_t n, bool pa
     return 0;
 }
 
-int process_impl(upe_gpu_ctx_t* c, const ProcessReq& q) {
+}  // namespace
+
+int upe::process_impl(upe_gpu_ctx_t* c, const ProcessReq& q) {
     // 1. validate
     if (!c) return fail("null context");
     const size_t n = q.n;
@@ -3528,7 +3107,7 @@ int process_impl(upe_gpu_ctx_t* c, const ProcessReq& q) {
     const bool emit = q.hdr != nullptr && n > 0;
     const PlanReq pq{n, emit, q.flow_hash != nullptr, q.tx != nullptr, host,
                      q.ring ? q.ring->per : 0, q.ring && q.ring->done};
-    const LdsPlan p = plan_lds(c->table.shape(c->neigh, c->tree_stage), pq, c->lb.no_lb);
+    const LdsPlan p = plan_lds(table_shape(c), pq, c->lb.no_lb);
     if (p.gb && c->stats.gb.reserve(n, (n + n / 4 + 64) & ~(size_t)3) != 0) return -1;   // either form
     // 5. the arguments
     Args a = fill_args(c, q, p);
@@ -3583,7 +3162,6 @@ int process_impl(upe_gpu_ctx_t* c, const ProcessReq& q) {
     c->have_batch = true;
     return 0;
 }
-}  // namespace
 
 extern "C" {
 
@@ -3631,292 +3209,6 @@ int upe_gpu_process_ring_emit(upe_gpu_ctx_t* c, uint8_t* d_frames, const uint64_
     ProcessReq q{d_frames, d_desc, d_verdict, n * count, stream};
     q.hdr = d_hdr;
     q.ring = &r;
-    return process_impl(c, q);
-}
-
-}  // extern "C"
-
-namespace {
-// The host round trip (upe_gpu_process_host / _emit): chunks of the caller's host batch through
-// a ring of device slots, H2D on one copy stream, classify on the context's stream, D2H on a
-// second copy stream.  In place: the rewritten span [lo, wb) of each chunk comes back.  Emit:
-// the verdicts and the 16-byte records come back (20 B per packet instead of the span: the
-// link's two directions share its bandwidth, so fewer bytes back let more go in), and when
-// apply_threads >= 0 the records are applied to the caller's frames on the host two chunks
-// behind, by the calling thread and `apply_threads` pool threads, while later chunks move.
-int host_roundtrip(upe_gpu_ctx_t* c, uint8_t* h_frames, size_t frames_bytes,
-                   const uint64_t* h_desc, uint32_t* h_verdict, upe_hdr_rec_t* h_hdr, size_t n,
-                   size_t chunk, bool emit, int apply_threads) {
-    if (!c) return fail("null context");
-    if (n && (!h_frames || !h_desc || !h_verdict || (emit && !h_hdr))) return fail("null host buffer");
-    DEV_SCOPE(c->device);
-    // default chunks (round-3 sweep, config B 1M): in place 256k (479 Mpps; 128k 406, 64k 359),
-    // emit 128k (559 Mpps; 256k 534, 64k 529)
-    if (chunk == 0) chunk = emit ? (size_t)1 << 17 : (size_t)1 << 18;
-    // emit: whole 64-packet groups per chunk, so that each chunk's compacted records (relative to
-    // its first packet) land where the batch's own layout puts them
-    if (emit) chunk = std::max<size_t>(64, chunk & ~(size_t)63);
-    if (!c->host.s_in) {
-        HIP_TRY(hipStreamCreateWithFlags(&c->host.s_in, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&c->host.s_out, hipStreamNonBlocking));
-        for (auto& sl : c->host.slots) {
-            HIP_TRY(hipEventCreateWithFlags(&sl.in_done, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&sl.k_done, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&sl.out_done, hipEventDisableTiming));
-        }
-    }
-    if (n == 0) {
-        if (upe_gpu_process(c, nullptr, nullptr, nullptr, 0, nullptr) != 0) return -1;
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return 0;
-    }
-    const bool apply = emit && apply_threads >= 0;
-    if (apply && apply_threads > 0 &&
-        (!c->host.pool || c->host.pool->th.size() != (size_t)apply_threads)) {
-        std::vector<int> cpus(CPU_SETSIZE);
-        const int k = upe_gpu_local_cpus(c->device, cpus.data(), cpus.size(), nullptr);
-        cpus.resize(k > 0 ? (size_t)k : 0);
-        c->host.pool.reset();
-        c->host.pool.reset(new ApplyPool((unsigned)apply_threads, cpus));
-    }
-    // Whatever happens below, no copy into the caller's buffers is left in flight on return.
-    struct Drain {
-        upe_gpu_ctx* c;
-        ~Drain() {
-            (void)hipStreamSynchronize(c->host.s_in);
-            (void)hipStreamSynchronize(c->stream);
-            (void)hipStreamSynchronize(c->host.s_out);
-            for (auto& sl : c->host.slots) sl.busy = false;
-        }
-    } drain{c};
-    const size_t nslots = c->host.nslots;
-    // copies back on their own stream: both link directions at once (issuing them on the copy-in
-    // stream after the next chunk's copy-in measured slower: B 332-344 vs 480 Mpps in place)
-    hipStream_t s_back = c->host.s_out;
-    const size_t lag = 2;   // emit: chunk k - lag is applied while chunk k is issued
-    struct Done {
-        size_t s, e, slot;
-        uint64_t lo;
-    };
-    std::vector<Done> pending;
-    // apply chunk d's records (and copy back its answered ARP requests, rewritten in place in
-    // the device slot, which the reference transmits from b->data, src/worker.c:40-52)
-    auto finish = [&](const Done& d) -> int {
-        auto& sl = c->host.slots[d.slot];
-        HIP_TRY(hipEventSynchronize(sl.out_done));
-        std::atomic<bool> replies{false};
-        auto job = [&](unsigned t, unsigned T) {
-            const size_t m = d.e - d.s, a0 = d.s + m * t / T, a1 = d.s + m * (t + 1) / T;
-            bool r = false;
-            // the compacted record of the range's first forwarded packet
-            size_t rec = a0 & ~(size_t)63;
-            for (size_t j = rec; j < a0; ++j) rec += UPE_VERDICT_CODE(h_verdict[j]) == UPE_V_FWD;
-            for (size_t i = a0; i < a1; ++i) {
-                r |= (h_verdict[i] & UPE_VF_ARP_REPLY) != 0;
-                if ((i & 63u) == 0) rec = i;
-                if (UPE_VERDICT_CODE(h_verdict[i]) == UPE_V_FWD) {
-                    if (apply) upe_hdr_apply(h_frames + (h_desc[i] >> 16), &h_hdr[rec]);
-                    ++rec;
-                }
-            }
-            if (r) replies.store(true, std::memory_order_relaxed);
-        };
-        if (c->host.pool && apply && apply_threads > 0) c->host.pool->run(job);
-        else job(0, 1);
-        if (replies.load())
-            for (size_t i = d.s; i < d.e; ++i)
-                if (h_verdict[i] & UPE_VF_ARP_REPLY) {
-                    const uint64_t off = h_desc[i] >> 16, len = h_desc[i] & 0xFFFFu;
-                    HIP_TRY(hipMemcpy(h_frames + off, sl.frames + (off - d.lo),
-                                      len < UPE_REWRITE_EXTENT ? len : UPE_REWRITE_EXTENT,
-                                      hipMemcpyDeviceToHost));
-                }
-        return 0;
-    };
-    // a chunk's copy-back (verdicts + records, or verdicts + the rewritten span), once its kernel
-    // is queued
-    auto issue_back = [&](size_t s, size_t e, size_t slot, uint64_t lo, uint64_t wb) -> int {
-        auto& sb = c->host.slots[slot];
-        const size_t m = e - s;
-        HIP_TRY(hipStreamWaitEvent(s_back, sb.k_done, 0));
-        HIP_TRY(hipMemcpyAsync(h_verdict + s, sb.verdict, m * sizeof(uint32_t),
-                               hipMemcpyDeviceToHost, s_back));
-        if (emit)
-            HIP_TRY(hipMemcpyAsync(h_hdr + s, sb.hdr, m * sizeof(upe_hdr_rec_t),
-                                   hipMemcpyDeviceToHost, s_back));
-        else
-            HIP_TRY(hipMemcpyAsync(h_frames + lo, sb.frames, (size_t)(wb - lo),
-                                   hipMemcpyDeviceToHost, s_back));
-        HIP_TRY(hipEventRecord(sb.out_done, s_back));
-        sb.busy = true;
-        sb.lo = lo;
-        sb.wb = wb;
-        return 0;
-    };
-    size_t k = 0;
-    for (size_t s = 0; s < n; s += chunk, ++k) {
-        const size_t e = n - s < chunk ? n : s + chunk, m = e - s;
-        // The chunk's byte ranges: [lo, hi) holds every frame's window (the kernel reads up to
-        // UPE_FRAME_TAIL bytes from a frame start), [lo, wb) every byte the kernel may rewrite.
-        // The scan of chunk k+1 overlaps the copies and kernel of chunk k.
-        uint64_t lo = ~0ull, hi = 0, wb = 0;
-        for (size_t i = s; i < e; ++i) {
-            const uint64_t off = h_desc[i] >> 16, len = h_desc[i] & 0xFFFFu;
-            if (off & 15u) return fail("frame offsets must be multiples of 16 (include/upe_gpu.h)");
-            lo = off < lo ? off : lo;
-            hi = off + UPE_FRAME_TAIL > hi ? off + UPE_FRAME_TAIL : hi;
-            const uint64_t w = off + (len < UPE_REWRITE_EXTENT ? len : UPE_REWRITE_EXTENT);
-            wb = w > wb ? w : wb;
-        }
-        if (hi > frames_bytes)
-            return fail("a frame window runs past frames_bytes (UPE_FRAME_TAIL bytes must follow "
-                        "every frame start)");
-        const size_t si = k % nslots;
-        auto& sl = c->host.slots[si];
-        if (emit && pending.size() >= lag) {   // the oldest finished before its slot is reused
-            if (finish(pending.front()) != 0) return -1;
-            pending.erase(pending.begin());
-        }
-        if (sl.busy) HIP_TRY(hipEventSynchronize(sl.out_done));   // the slot's last D2H is done
-        sl.busy = false;
-        const size_t span = (size_t)(hi - lo);
-        if (sl.frames.reserve(span, span + span / 4) != 0) return -1;
-        // (verdict, made after desc, holds the slot's packet capacity)
-        if (m > sl.verdict.cap || (emit && !sl.hdr)) {
-            const size_t cap = std::max(m, sl.verdict.cap);
-            sl.desc.reset();
-            sl.verdict.reset();
-            sl.hdr.reset();
-            if (sl.desc.reserve(cap, cap) != 0 || sl.verdict.reserve(cap, cap) != 0 ||
-                (emit && sl.hdr.reserve(cap, cap) != 0))
-                return -1;
-        }
-        // In place: a chunk whose bytes interleave with an earlier chunk's (descriptors in any
-        // order, e.g. pool addresses) must read them only after that chunk's copy-back has
-        // landed: its own copy-back rewrites its whole span, and would otherwise put back the
-        // earlier chunk's frames as they were before they were processed.  (Emit mode copies
-        // no frame bytes back.)
-        if (!emit)
-            for (auto& other : c->host.slots)
-                if (&other != &sl && other.busy && other.lo < hi && lo < other.wb)
-                    HIP_TRY(hipStreamWaitEvent(c->host.s_in, other.out_done, 0));
-        HIP_TRY(hipMemcpyAsync(sl.frames, h_frames + lo, span, hipMemcpyHostToDevice, c->host.s_in));
-        HIP_TRY(hipMemcpyAsync(sl.desc, h_desc + s, m * sizeof(uint64_t), hipMemcpyHostToDevice,
-                               c->host.s_in));
-        HIP_TRY(hipEventRecord(sl.in_done, c->host.s_in));
-        HIP_TRY(hipStreamWaitEvent(c->stream, sl.in_done, 0));
-        // the descriptors keep their offsets relative to h_frames: hand the kernel a base that
-        // maps offset lo onto the slot (lo is a multiple of 16, so the base stays aligned)
-        uint8_t* base = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(sl.frames.p) - lo);
-        // (the host-path kernel instantiation: profiles keep these launches apart)
-        ProcessReq q{base, sl.desc, sl.verdict, m, nullptr};
-        q.hdr = emit ? sl.hdr.p : nullptr;
-        q.host = true;
-        if (process_impl(c, q) != 0) return -1;
-        HIP_TRY(hipEventRecord(sl.k_done, c->stream));
-        if (issue_back(s, e, si, lo, wb) != 0) return -1;
-        if (emit) pending.push_back(Done{s, e, si, lo});
-    }
-    for (const Done& d : pending)
-        if (finish(d) != 0) return -1;
-    HIP_TRY(hipStreamSynchronize(s_back));
-    return 0;
-}
-}  // namespace
-
-extern "C" {
-
-int upe_gpu_process_host(upe_gpu_ctx_t* c, uint8_t* h_frames, size_t frames_bytes,
-                         const uint64_t* h_desc, uint32_t* h_verdict, size_t n, size_t chunk) {
-    return host_roundtrip(c, h_frames, frames_bytes, h_desc, h_verdict, nullptr, n, chunk, false,
-                          -1);
-}
-
-int upe_gpu_process_host_emit(upe_gpu_ctx_t* c, uint8_t* h_frames, size_t frames_bytes,
-                              const uint64_t* h_desc, uint32_t* h_verdict, upe_hdr_rec_t* h_hdr,
-                              size_t n, size_t chunk, int apply_threads) {
-    if (apply_threads > 64) return fail("apply_threads must be at most 64");
-    return host_roundtrip(c, h_frames, frames_bytes, h_desc, h_verdict, h_hdr, n, chunk, true,
-                          apply_threads);
-}
-
-void* upe_gpu_host_alloc(size_t bytes) {
-    void* p = nullptr;
-    if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) {
-        fail("hipHostMalloc failed");
-        return nullptr;
-    }
-    return p;
-}
-
-int upe_gpu_host_free(void* p) {
-    if (p) HIP_TRY(hipHostFree(p));
-    return 0;
-}
-
-int upe_gpu_host_register(void* p, size_t bytes) {
-    if (!p || !bytes) return fail("null or empty host buffer");
-    HIP_TRY(hipHostRegister(p, bytes, hipHostRegisterMapped | hipHostRegisterPortable));
-    return 0;
-}
-
-int upe_gpu_host_unregister(void* p) {
-    if (!p) return fail("null host buffer");
-    HIP_TRY(hipHostUnregister(p));
-    return 0;
-}
-
-}  // extern "C"
-
-namespace {
-// The device address of page-locked, mapped host memory; nullptr (and an error) for anything
-// else, so that a kernel never dereferences an unmapped host address.
-template <typename T>
-T* mapped(T* h, const char* what) {
-    void* d = nullptr;
-    if (hipHostGetDevicePointer(&d, const_cast<void*>(static_cast<const void*>(h)), 0) != hipSuccess ||
-        !d) {
-        (void)hipGetLastError();
-        fail(std::string(what) + " is not pinned, mapped host memory (upe_gpu_host_alloc / "
-             "upe_gpu_host_register)");
-        return nullptr;
-    }
-    return static_cast<T*>(d);
-}
-}  // namespace
-
-extern "C" {
-
-int upe_gpu_process_mapped(upe_gpu_ctx_t* c, uint8_t* h_frames, const uint64_t* h_desc,
-                           uint32_t* h_verdict, size_t n, void* stream) {
-    if (!c) return fail("null context");
-    DEV_SCOPE(c->device);
-    if (n == 0) return upe_gpu_process(c, nullptr, nullptr, nullptr, 0, stream);
-    if (!h_frames || !h_desc || !h_verdict) return fail("null host buffer");
-    uint8_t* f = mapped(h_frames, "h_frames");
-    const uint64_t* d = f ? mapped(h_desc, "h_desc") : nullptr;
-    uint32_t* v = d ? mapped(h_verdict, "h_verdict") : nullptr;
-    if (!v) return -1;
-    ProcessReq q{f, d, v, n, stream};
-    q.host = true;
-    return process_impl(c, q);
-}
-
-int upe_gpu_process_mapped_emit(upe_gpu_ctx_t* c, uint8_t* h_frames, const uint64_t* h_desc,
-                                uint32_t* h_verdict, upe_hdr_rec_t* h_hdr, size_t n,
-                                void* stream) {
-    if (!c) return fail("null context");
-    DEV_SCOPE(c->device);
-    if (n == 0) return upe_gpu_process(c, nullptr, nullptr, nullptr, 0, stream);
-    if (!h_frames || !h_desc || !h_verdict || !h_hdr) return fail("null host buffer");
-    uint8_t* f = mapped(h_frames, "h_frames");
-    const uint64_t* d = f ? mapped(h_desc, "h_desc") : nullptr;
-    uint32_t* v = d ? mapped(h_verdict, "h_verdict") : nullptr;
-    upe_hdr_rec_t* h = v ? mapped(h_hdr, "h_hdr") : nullptr;
-    if (!h) return -1;
-    ProcessReq q{f, d, v, n, stream};
-    q.hdr = h;
-    q.host = true;
     return process_impl(c, q);
 }
 
@@ -3983,406 +3275,6 @@ int upe_gpu_compact(upe_gpu_ctx_t* c, const uint32_t* d_verdict, size_t n, uint3
                        c->compact_counts, nb, d_index,
                        reinterpret_cast<unsigned long long*>(d_count));
     HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// The RX thread's dispatch (reference src/rx_pcap.c:19-25,67-80); the kernels are upe_rx.hip's.
-// ev: NULL, or four events around the three passes.
-static int rx_dispatch(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc, size_t n,
-                       uint32_t rings, uint32_t rr_start, uint32_t* d_ring, uint32_t* d_flow_hash,
-                       uint32_t* d_index, uint64_t* d_desc_out, uint64_t* d_counts, void* stream,
-                       hipEvent_t* ev) {
-    if (!c) return fail("null context");
-    if (rings == 0 || (rings & (rings - 1)) != 0 || rings > UPE_RX_RINGS_MAX)
-        return fail("rings must be a power of two between 1 and " +
-                    std::to_string(UPE_RX_RINGS_MAX));
-    if (!d_counts || (n && (!d_frames || !d_desc || !d_ring || !d_index)))
-        return fail("null buffer");
-    if (n > 0xFFFFFFFFull - UPE_RX_BLOCK) return fail("n must fit in 32 bits");
-    DEV_SCOPE(c->device);
-    hipStream_t s = pick(c, stream);
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(d_counts, 0, (rings + 1) * sizeof(uint64_t), s));
-        return 0;
-    }
-    const size_t need = upe_rx_scratch_bytes((uint32_t)n, rings);
-    if (c->rx_scratch.reserve(need, need + need / 4) != 0) return -1;
-    HIP_TRY(upe_rx_launch(d_frames, d_desc, (uint32_t)n, rings, rr_start & (rings - 1), d_ring,
-                          d_flow_hash, d_index, d_desc_out, d_counts,
-                          reinterpret_cast<uint32_t*>(c->rx_scratch.p), s, ev));
-    return 0;
-}
-
-int upe_gpu_rx_dispatch(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc, size_t n,
-                        uint32_t rings, uint32_t rr_start, uint32_t* d_ring, uint32_t* d_flow_hash,
-                        uint32_t* d_index, uint64_t* d_desc_out, uint64_t* d_counts, void* stream) {
-    return rx_dispatch(c, d_frames, d_desc, n, rings, rr_start, d_ring, d_flow_hash, d_index,
-                       d_desc_out, d_counts, stream, nullptr);
-}
-
-// Diagnostic (tools/rx_dispatch_time.py; not in the header): one dispatch of n > 0 packets with
-// HIP events around each pass; ms[0..2] = the hash, scan and scatter pass.  Synchronous.
-int upe_gpu_rx_dispatch_timed(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc,
-                              size_t n, uint32_t rings, uint32_t rr_start, uint32_t* d_ring,
-                              uint32_t* d_flow_hash, uint32_t* d_index, uint64_t* d_desc_out,
-                              uint64_t* d_counts, void* stream, float* ms) {
-    if (!c || !ms || n == 0) return fail("null context, no output or an empty batch");
-    DEV_SCOPE(c->device);
-    Events<4> ev;
-    if (ev.create() != 0 ||
-        rx_dispatch(c, d_frames, d_desc, n, rings, rr_start, d_ring, d_flow_hash, d_index,
-                    d_desc_out, d_counts, stream, ev.e) != 0)
-        return -1;
-    HIP_TRY(hipEventSynchronize(ev.e[3]));
-    for (int k = 0; k < 3; ++k)
-        if (ev.elapsed(&ms[k], k, k + 1) != 0) return -1;
-    return 0;
-}
-
-// The egress batch builder (reference src/worker.c:240-243, 287-303: the frames queued for
-// tx_send_batch, in order); the kernels are upe_egress.hip's.  ev: NULL, or four events around
-// the three passes.
-static int egress_pack(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc,
-                       const uint32_t* d_verdict, const upe_hdr_rec_t* d_hdr, size_t n,
-                       uint8_t* d_out, size_t out_bytes, uint64_t* d_out_desc,
-                       uint32_t* d_out_index, upe_egress_info_t* d_info, void* stream,
-                       hipEvent_t* ev) {
-    if (!c) return fail("null context");
-    if (!d_info || (n && (!d_frames || !d_desc || !d_verdict || !d_out || !d_out_desc)))
-        return fail("null buffer");
-    if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0 ||
-        (reinterpret_cast<uintptr_t>(d_frames) & 15u) != 0 ||
-        (reinterpret_cast<uintptr_t>(d_hdr) & 15u) != 0)
-        return fail("d_out, d_frames and d_hdr must be 16-byte aligned");
-    if (n > 0xFFFFFFFFull - UPE_EGRESS_BLOCK) return fail("n must fit in 32 bits");
-    DEV_SCOPE(c->device);
-    hipStream_t s = pick(c, stream);
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(d_info, 0, sizeof(upe_egress_info_t), s));
-        return 0;
-    }
-    // where the frames end is not known here: they count up to the end of their allocation
-    const uintptr_t fr = reinterpret_cast<uintptr_t>(d_frames);
-    const uintptr_t out = reinterpret_cast<uintptr_t>(d_out);
-    uintptr_t fr_end = fr + 1;
-    hipDeviceptr_t abase = nullptr;
-    size_t asize = 0;
-    if (hipMemGetAddressRange(&abase, &asize, const_cast<uint8_t*>(d_frames)) == hipSuccess)
-        fr_end = reinterpret_cast<uintptr_t>(abase) + asize;
-    else
-        (void)hipGetLastError();   // not a device allocation's pointer (mapped host memory)
-    if (out < fr_end && fr < out + (out_bytes ? out_bytes : 1))
-        return fail("d_out overlaps d_frames");
-    const size_t need = upe_egress_scratch_bytes((uint32_t)n);
-    if (c->eg_scratch.reserve(need, need + need / 4) != 0) return -1;
-    HIP_TRY(upe_egress_launch(d_frames, d_desc, d_verdict, d_hdr, (uint32_t)n, d_out, out_bytes,
-                              d_out_desc, d_out_index, d_info, c->eg_scratch.p, s, ev));
-    return 0;
-}
-
-int upe_gpu_egress_pack(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc,
-                        const uint32_t* d_verdict, const upe_hdr_rec_t* d_hdr, size_t n,
-                        uint8_t* d_out, size_t out_bytes, uint64_t* d_out_desc,
-                        uint32_t* d_out_index, upe_egress_info_t* d_info, void* stream) {
-    return egress_pack(c, d_frames, d_desc, d_verdict, d_hdr, n, d_out, out_bytes, d_out_desc,
-                       d_out_index, d_info, stream, nullptr);
-}
-
-// Diagnostic (tools/egress_pack_time.py; not in the header): one pack of n > 0 packets with HIP
-// events around each pass, then a plain device-to-device copy of the packed bytes (info.bytes,
-// d_out -> d_copy, out_bytes of room) on the same stream: the floor of the copy pass.
-// ms[0..3] = the size, scan and copy pass and that copy.  Synchronous.
-int upe_gpu_egress_pack_timed(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc,
-                              const uint32_t* d_verdict, const upe_hdr_rec_t* d_hdr, size_t n,
-                              uint8_t* d_out, size_t out_bytes, uint64_t* d_out_desc,
-                              uint32_t* d_out_index, upe_egress_info_t* d_info, uint8_t* d_copy,
-                              void* stream, float* ms) {
-    if (!c || !ms || !d_copy || n == 0)
-        return fail("null context, no output or an empty batch");
-    DEV_SCOPE(c->device);
-    hipStream_t s = pick(c, stream);
-    Events<6> ev;
-    if (ev.create() != 0 ||
-        egress_pack(c, d_frames, d_desc, d_verdict, d_hdr, n, d_out, out_bytes, d_out_desc,
-                    d_out_index, d_info, stream, ev.e) != 0)
-        return -1;
-    upe_egress_info_t info = {};
-    if (hipMemcpyAsync(&info, d_info, sizeof(info), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return fail("reading the pack's info");
-    if (hipEventRecord(ev.e[4], s) != hipSuccess ||
-        hipMemcpyAsync(d_copy, d_out, info.bytes, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-        hipEventRecord(ev.e[5], s) != hipSuccess || hipEventSynchronize(ev.e[5]) != hipSuccess)
-        return fail("the device-to-device copy");
-    for (int k = 0; k < 3; ++k)
-        if (ev.elapsed(&ms[k], k, k + 1) != 0) return -1;
-    return ev.elapsed(&ms[3], 4, 5);
-}
-
-// The ingress batch builder (reference src/worker.c:255-307 hands the worker pktbuf handles;
-// upe_worker.c gathers them per packet on the CPU); the kernels are upe_ingress.hip's.  ev: NULL,
-// or four events around the three passes.
-static int ingress_gather(upe_gpu_ctx_t* c, const uint8_t* pool, size_t pool_bytes, size_t stride,
-                          const uint32_t* d_slot, size_t n, int mode, uint8_t* d_out,
-                          size_t out_bytes, uint64_t* d_desc, uint64_t* d_timestamp,
-                          uint32_t* d_ctrl, upe_ingress_info_t* d_info, void* stream,
-                          hipEvent_t* ev) {
-    if (!c) return fail("null context");
-    if (!d_info || (n && (!pool || !d_slot || !d_desc))) return fail("null buffer");
-    if (mode != UPE_INGRESS_REF && mode != UPE_INGRESS_WINDOW && mode != UPE_INGRESS_FULL)
-        return fail("unknown ingress mode");
-    if (stride % 16 != 0 || stride < 16 + UPE_FRAME_TAIL)
-        return fail("stride must be a multiple of 16 and at least 16 + UPE_FRAME_TAIL");
-    if (pool_bytes < stride || pool_bytes > (1ull << 36))
-        return fail("pool_bytes must be at least stride and at most 2^36");
-    if ((reinterpret_cast<uintptr_t>(pool) & 15u) != 0) return fail("pool must be 16-byte aligned");
-    if (mode == UPE_INGRESS_REF ? (d_out != nullptr || out_bytes != 0) : (n && !d_out))
-        return fail("d_out goes with WINDOW and FULL mode only");
-    if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail("d_out must be 16-byte aligned");
-    if (n > 0xFFFFFFFFull - UPE_INGRESS_BLOCK) return fail("n must fit in 32 bits");
-    if (mode == UPE_INGRESS_WINDOW && out_bytes / UPE_HDR_WINDOW < n)
-        return fail("d_out is smaller than n header windows");
-    DEV_SCOPE(c->device);
-    hipStream_t s = pick(c, stream);
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(d_info, 0, sizeof(upe_ingress_info_t), s));
-        HIP_TRY(hipMemsetAsync(&d_info->first_bad, 0xFF, sizeof(uint64_t), s));
-        HIP_TRY(hipMemsetAsync(&d_info->first_ctrl, 0xFF, sizeof(uint64_t), s));
-        return 0;
-    }
-    // the pool as the kernels address it: device memory, or pinned host memory through its mapping
-    hipPointerAttribute_t attr = {};
-    if (hipPointerGetAttributes(&attr, pool) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail("pool is neither device memory nor pinned, mapped host memory");
-    }
-    const uint8_t* dpool = pool;
-    uintptr_t lo = reinterpret_cast<uintptr_t>(pool), hi = lo + pool_bytes;
-    if (attr.type == hipMemoryTypeHost) {
-        dpool = mapped(pool, "pool");
-        if (!dpool) return -1;
-        lo = reinterpret_cast<uintptr_t>(dpool), hi = lo + pool_bytes;
-    } else if (attr.type == hipMemoryTypeDevice) {
-        // where the caller's buffers end is not checked against the allocation, but d_out is kept
-        // out of all of it, as upe_gpu_egress_pack keeps it out of d_frames'
-        hipDeviceptr_t abase = nullptr;
-        size_t asize = 0;
-        if (hipMemGetAddressRange(&abase, &asize, const_cast<uint8_t*>(pool)) == hipSuccess) {
-            const uintptr_t end = reinterpret_cast<uintptr_t>(abase) + asize;
-            if (end > hi) hi = end;
-        } else {
-            (void)hipGetLastError();
-        }
-    } else {
-        return fail("pool is neither device memory nor pinned, mapped host memory");
-    }
-    if (d_out) {
-        const uintptr_t out = reinterpret_cast<uintptr_t>(d_out);
-        if (out < hi && lo < out + (out_bytes ? out_bytes : 1)) return fail("d_out overlaps the pool");
-    }
-    const size_t need = upe_ingress_scratch_bytes((uint32_t)n);
-    if (c->in_scratch.reserve(need, need + need / 4) != 0) return -1;
-    HIP_TRY(upe_ingress_launch(dpool, pool_bytes, stride, d_slot, (uint32_t)n, mode, d_out,
-                               out_bytes, d_desc, d_timestamp, d_ctrl, d_info, c->in_scratch.p, s,
-                               ev));
-    return 0;
-}
-
-int upe_gpu_ingress_gather(upe_gpu_ctx_t* c, const uint8_t* pool, size_t pool_bytes, size_t stride,
-                           const uint32_t* d_slot, size_t n, int mode, uint8_t* d_out,
-                           size_t out_bytes, uint64_t* d_desc, uint64_t* d_timestamp,
-                           uint32_t* d_ctrl, upe_ingress_info_t* d_info, void* stream) {
-    return ingress_gather(c, pool, pool_bytes, stride, d_slot, n, mode, d_out, out_bytes, d_desc,
-                          d_timestamp, d_ctrl, d_info, stream, nullptr);
-}
-
-// Diagnostic (tools/ingress_gather_time.py; not in the header): one gather of n > 0 packets with
-// HIP events around each pass, then a plain hipMemcpyAsync of copy_bytes from copy_src to copy_dst
-// on the same stream (device to device, or host to device when copy_src is pinned host memory):
-// the yardstick for the bytes the gather moves.  ms[0..3] = the size, scan and write pass and that
-// copy.  Synchronous.
-int upe_gpu_ingress_gather_timed(upe_gpu_ctx_t* c, const uint8_t* pool, size_t pool_bytes,
-                                 size_t stride, const uint32_t* d_slot, size_t n, int mode,
-                                 uint8_t* d_out, size_t out_bytes, uint64_t* d_desc,
-                                 uint64_t* d_timestamp, uint32_t* d_ctrl,
-                                 upe_ingress_info_t* d_info, const uint8_t* copy_src,
-                                 uint8_t* copy_dst, size_t copy_bytes, void* stream, float* ms) {
-    if (!c || !ms || !copy_src || !copy_dst || n == 0)
-        return fail("null context, no output or an empty batch");
-    DEV_SCOPE(c->device);
-    hipStream_t s = pick(c, stream);
-    Events<6> ev;
-    if (ev.create() != 0 ||
-        ingress_gather(c, pool, pool_bytes, stride, d_slot, n, mode, d_out, out_bytes, d_desc,
-                       d_timestamp, d_ctrl, d_info, stream, ev.e) != 0)
-        return -1;
-    if (hipStreamSynchronize(s) != hipSuccess) return fail("waiting for the gather");
-    if (hipEventRecord(ev.e[4], s) != hipSuccess ||
-        hipMemcpyAsync(copy_dst, copy_src, copy_bytes, hipMemcpyDefault, s) != hipSuccess ||
-        hipEventRecord(ev.e[5], s) != hipSuccess || hipEventSynchronize(ev.e[5]) != hipSuccess)
-        return fail("the yardstick copy");
-    for (int k = 0; k < 3; ++k)
-        if (ev.elapsed(&ms[k], k, k + 1) != 0) return -1;
-    return ev.elapsed(&ms[3], 4, 5);
-}
-
-}  // extern "C"
-
-namespace {
-
-// The table writes of handle_control_packet, restated on the caller's host slot arrays.
-// arp_update, reference src/arp_table.c:26-53: home slot ip & (cap-1), linear probe, insert at
-// the first free slot or update the slot holding ip, at most cap probes.
-void host_arp_update(upe_arp_entry_t* t, size_t cap, uint32_t ip, const uint8_t* mac,
-                     int64_t now) {
-    const size_t idx = ip & (cap - 1);
-    for (size_t k = 0; k < cap; ++k) {
-        upe_arp_entry_t& e = t[(idx + k) & (cap - 1)];
-        if (!e.valid || e.ip == ip) {
-            if (!e.valid) {
-                e.valid = true;
-                e.ip = ip;
-            }
-            memcpy(e.mac, mac, 6);
-            e.update_at = now;
-            return;
-        }
-    }
-}
-
-// ndp_update, reference src/ndp_table.c:39-65 (hash_ipv6 :6-17: XOR of the address's four
-// native-endian words, & (cap-1)).
-void host_ndp_update(upe_ndp_entry_t* t, size_t cap, const uint8_t* ip, const uint8_t* mac,
-                     int64_t now) {
-    const uint32_t h = le32(ip) ^ le32(ip + 4) ^ le32(ip + 8) ^ le32(ip + 12);
-    const size_t idx = h & (cap - 1);
-    for (size_t k = 0; k < cap; ++k) {
-        upe_ndp_entry_t& e = t[(idx + k) & (cap - 1)];
-        if (!e.valid || memcmp(e.ip, ip, 16) == 0) {
-            if (!e.valid) {
-                e.valid = true;
-                memcpy(e.ip, ip, 16);
-            }
-            memcpy(e.mac, mac, 6);
-            e.update_at = now;
-            return;
-        }
-    }
-}
-
-}  // namespace
-
-extern "C" {
-
-int upe_gpu_process_segmented(upe_gpu_ctx_t* c, uint8_t* d_frames, const uint64_t* d_desc,
-                              uint32_t* d_verdict, size_t n, upe_arp_entry_t* arp,
-                              size_t arp_capacity, upe_ndp_entry_t* ndp, size_t ndp_capacity,
-                              int64_t now, size_t* n_writes, void* stream) {
-    if (!c) return fail("null context");
-    if (n_writes) *n_writes = 0;
-    if (n > 0xFFFFFFFFull - kCompactBlock) return fail("batch too large (n must fit in 32 bits)");
-    if (n && (!d_frames || !d_desc || !d_verdict)) return fail("null batch buffer");
-    if ((arp_capacity && !arp) || (ndp_capacity && !ndp)) return fail("null neighbour table");
-    if ((arp_capacity & (arp_capacity - 1)) || (ndp_capacity & (ndp_capacity - 1)))
-        return fail("neighbour table capacities must be powers of two");
-    if (n == 0) return upe_gpu_process(c, d_frames, d_desc, d_verdict, 0, stream);
-    DEV_SCOPE(c->device);
-    hipStream_t s = pick(c, stream);
-    // 1. mark and list the table-writing control packets, in packet order
-    if (n > c->seg.index.cap) {   // (the last one made: all are there when it is)
-        c->seg.marks.reset();
-        c->seg.index.reset();
-        if (c->seg.count.reserve(1, 1) != 0 ||   // once
-            c->seg.marks.reserve(n, n) != 0 || c->seg.index.reserve(n, n) != 0)
-            return -1;
-    }
-    hipLaunchKernelGGL(upe_ctrl_mark, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s,
-                       d_frames, d_desc, (uint32_t)n, c->seg.marks);
-    HIP_TRY(hipGetLastError());
-    if (upe_gpu_compact(c, c->seg.marks, n, 1u, c->seg.index, c->seg.count, s) != 0) return -1;
-    uint64_t cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&cnt, c->seg.count, sizeof cnt, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (cnt == 0) return upe_gpu_process(c, d_frames, d_desc, d_verdict, n, stream);
-    // 2. their bytes, gathered before any segment runs (the ARP reply is built in place)
-    if (cnt > c->seg.lens.cap) {   // (the last one made)
-        c->seg.win.reset();
-        c->seg.lens.reset();
-        if (c->seg.win.reserve(cnt * kCtrlWin, cnt * kCtrlWin) != 0 ||
-            c->seg.lens.reserve(cnt, cnt) != 0)
-            return -1;
-    }
-    hipLaunchKernelGGL(upe_ctrl_gather, dim3((uint32_t)cnt), dim3(kCtrlWin), 0, s, d_frames,
-                       d_desc, c->seg.index, c->seg.win, c->seg.lens);
-    HIP_TRY(hipGetLastError());
-    std::vector<uint32_t> idx(cnt), lens(cnt);
-    std::vector<uint8_t> win(cnt * kCtrlWin);
-    HIP_TRY(hipMemcpyAsync(idx.data(), c->seg.index, cnt * sizeof(uint32_t),
-                           hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(lens.data(), c->seg.lens, cnt * sizeof(uint32_t),
-                           hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(win.data(), c->seg.win, win.size(), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    // 3. segments: up to and including each control packet, then its table write
-    size_t start = 0, writes = 0;
-    std::vector<uint8_t> full;
-    for (uint64_t j = 0; j < cnt; ++j) {
-        const size_t k = idx[j];
-        if (upe_gpu_process(c, d_frames, d_desc + start, d_verdict + start, k + 1 - start,
-                            stream) != 0)
-            return -1;
-        start = k + 1;
-        const uint8_t* b = win.data() + j * kCtrlWin;
-        const uint32_t len = lens[j];
-        bool wrote = false;
-        if (b[12] == 0x08 && b[13] == 0x06) {
-            // ARP learn, src/worker.c:30-39: spa (network order) -> host order, sha
-            if (arp_capacity) {
-                const uint32_t spa = (uint32_t)b[28] << 24 | (uint32_t)b[29] << 16 |
-                                     (uint32_t)b[30] << 8 | (uint32_t)b[31];
-                host_arp_update(arp, arp_capacity, spa, b + 22, now);
-                wrote = true;
-            }
-        } else {
-            // NS / NA option walk, src/worker.c:64-95, over the whole frame when it is long.
-            // This reads len bytes at the frame start: the call takes full frames only
-            // (include/upe_gpu.h), never the UPE_FRAME_TAIL-byte header windows of the host path.
-            const uint8_t* f = b;
-            if (len > kCtrlWin) {
-                uint64_t d = 0;
-                HIP_TRY(hipMemcpy(&d, d_desc + k, sizeof d, hipMemcpyDeviceToHost));
-                full.assign(len, 0);
-                HIP_TRY(hipMemcpy(full.data(), d_frames + (d >> 16), len, hipMemcpyDeviceToHost));
-                f = full.data();
-            }
-            const bool ns = f[54] == 135;
-            for (size_t off = 78; off + 2 <= len;) {
-                // uint8_t opt_len, as the reference's (src/worker.c:73): 32 wraps to 0, 33 to 8
-                const uint32_t ot = f[off], ol = (uint8_t)(f[off + 1] * 8u);
-                if (ol == 0 || off + ol > len) break;
-                if (ol >= 8 && ((ns && ot == 1) || (!ns && ot == 2))) {
-                    if (ndp_capacity) {
-                        host_ndp_update(ndp, ndp_capacity, ns ? f + 22 : f + 62, f + off + 2, now);
-                        wrote = true;
-                    }
-                    break;
-                }
-                off += ol;
-            }
-        }
-        if (wrote) {
-            ++writes;
-            // the next segment reads the new snapshot (load_neigh waits for the context's
-            // stream; a caller stream is drained first)
-            if (s != c->stream) HIP_TRY(hipStreamSynchronize(s));
-            if (upe_gpu_load_neigh(c, arp, arp_capacity, ndp, ndp_capacity) != 0) return -1;
-        }
-    }
-    if (start < n &&
-        upe_gpu_process(c, d_frames, d_desc + start, d_verdict + start, n - start, stream) != 0)
-        return -1;
-    HIP_TRY(hipStreamSynchronize(s));
-    if (n_writes) *n_writes = writes;
     return 0;
 }
 
@@ -4485,95 +3377,6 @@ int upe_gpu_reset_stats(upe_gpu_ctx_t* c) {
                                c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_batch = false;
-    return 0;
-}
-
-// The worker's latency histogram (reference src/worker.c:120-122 ... 249-251 per packet,
-// src/latency.c:41-59); the kernel is upe_latency.hip's.
-int upe_gpu_set_tsc(upe_gpu_ctx_t* c, double cycles_per_ns) {
-    if (!c) return fail("null context");
-    if (!(cycles_per_ns > 0.0 && cycles_per_ns <= DBL_MAX))
-        return fail("cycles_per_ns must be finite and > 0");
-    c->cycles_per_ns = cycles_per_ns;
-    return 0;
-}
-
-static int latency_check(upe_gpu_ctx_t* c, const uint64_t* d_timestamp, size_t n) {
-    if (!c) return fail("null context");
-    if (n && !d_timestamp) return fail("null buffer");
-    if (n > 0xFFFFFFFFull - UPE_LATENCY_BLOCK) return fail("n must fit in 32 bits");
-    if (!(c->cycles_per_ns > 0.0))
-        return fail("no calibration: upe_gpu_set_tsc has not succeeded on this context");
-    return 0;
-}
-
-// at most four workgroups per CU, each striding over the batch; UPE_GPU_GRID_CAP lowers it
-static uint32_t latency_grid(const upe_gpu_ctx_t* c) {
-    const uint32_t g = 4u * (uint32_t)c->cus;
-    return c->grid_cap && c->grid_cap < g ? c->grid_cap : g;
-}
-
-int upe_gpu_latency_record(upe_gpu_ctx_t* c, const uint64_t* d_timestamp,
-                           const uint32_t* d_verdict, size_t n, uint64_t now, void* stream) {
-    if (latency_check(c, d_timestamp, n) != 0) return -1;
-    if (n == 0) return 0;
-    DEV_SCOPE(c->device);
-    HIP_TRY(upe_latency_launch(d_timestamp, d_verdict, (uint32_t)n, now, c->cycles_per_ns,
-                               c->lat_hist.p, latency_grid(c), pick(c, stream)));
-    return 0;
-}
-
-// Diagnostic (tools/latency_time.py; not in the header): one upe_gpu_latency_record of n > 0
-// packets between two HIP events, then a plain hipMemcpyAsync of copy_bytes (device to device) on
-// the same stream between two more: the yardstick for the bytes the call reads.  ms[0] = the
-// launch, ms[1] = the copy.  Synchronous.
-int upe_gpu_latency_record_timed(upe_gpu_ctx_t* c, const uint64_t* d_timestamp,
-                                 const uint32_t* d_verdict, size_t n, uint64_t now,
-                                 const uint8_t* copy_src, uint8_t* copy_dst, size_t copy_bytes,
-                                 void* stream, float* ms) {
-    if (!ms || !copy_src || !copy_dst || n == 0) return fail("no output or an empty batch");
-    if (latency_check(c, d_timestamp, n) != 0) return -1;
-    DEV_SCOPE(c->device);
-    hipStream_t s = pick(c, stream);
-    Events<4> ev;
-    if (ev.create() != 0) return -1;
-    HIP_TRY(hipEventRecord(ev.e[0], s));
-    HIP_TRY(upe_latency_launch(d_timestamp, d_verdict, (uint32_t)n, now, c->cycles_per_ns,
-                               c->lat_hist.p, latency_grid(c), s));
-    HIP_TRY(hipEventRecord(ev.e[1], s));
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipEventRecord(ev.e[2], s));
-    HIP_TRY(hipMemcpyAsync(copy_dst, copy_src, copy_bytes, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipEventRecord(ev.e[3], s));
-    HIP_TRY(hipEventSynchronize(ev.e[3]));
-    if (ev.elapsed(&ms[0], 0, 1) != 0) return -1;
-    return ev.elapsed(&ms[1], 2, 3);
-}
-
-int upe_gpu_get_latency(upe_gpu_ctx_t* c, upe_latency_hist_t* out) {
-    if (!c || !out) return fail("null argument");
-    DEV_SCOPE(c->device);
-    HIP_TRY(hipDeviceSynchronize());
-    std::vector<unsigned long long> img(kLatWords);
-    HIP_TRY(hipMemcpy(img.data(), c->lat_hist.p, kLatWords * sizeof(unsigned long long),
-                      hipMemcpyDeviceToHost));
-    upe_latency_init(out);
-    for (size_t r = 0; r < UPE_LATENCY_REPLICAS; ++r) {
-        upe_latency_hist_t h;
-        memcpy(&h, &img[r * UPE_LATENCY_REPLICA_WORDS], sizeof h);
-        upe_latency_merge(out, &h);
-    }
-    return 0;
-}
-
-int upe_gpu_reset_latency(upe_gpu_ctx_t* c) {
-    if (!c) return fail("null context");
-    DEV_SCOPE(c->device);
-    HIP_TRY(hipDeviceSynchronize());   // launches on any stream have added what they add
-    std::vector<unsigned long long> img;
-    latency_init_image(img);
-    HIP_TRY(hipMemcpy(c->lat_hist.p, img.data(), kLatWords * sizeof(unsigned long long),
-                      hipMemcpyHostToDevice));
     return 0;
 }
 

@@ -36,9 +36,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/upe_gpu.h"
-#include "upe_dev.h"
-#include "upe_ingress.h"
+#include "upe_ctx.h"
 
 namespace {
 
@@ -458,13 +456,14 @@ Tab tab_of(void* scratch, uint32_t T) {
     return t;
 }
 
-}  // namespace
-
+// Bytes of scratch one gather of n packets needs (n > 0).
 size_t upe_ingress_scratch_bytes(uint32_t n) {
     const size_t tp = ((size_t)tiles_of(n) + 1u) & ~(size_t)1u;
     return tp * (sizeof(uint64_t) + 6 * sizeof(uint32_t)) + (size_t)n * sizeof(uint32_t);
 }
 
+// Queue the passes on `s`, with the arguments as ingress_gather has checked them.  A pass that a
+// mode does not launch leaves its pair of events back to back.
 hipError_t upe_ingress_launch(const uint8_t* pool, uint64_t pool_bytes, uint64_t stride,
                               const uint32_t* slot, uint32_t n, int mode, uint8_t* out,
                               uint64_t out_bytes, uint64_t* desc, uint64_t* timestamp,
@@ -511,3 +510,106 @@ hipError_t upe_ingress_launch(const uint8_t* pool, uint64_t pool_bytes, uint64_t
     if ((e = hipGetLastError()) != hipSuccess) return e;
     return ev ? hipEventRecord(ev[3], s) : hipSuccess;
 }
+
+using namespace upe;
+
+// The ingress batch builder (reference src/worker.c:255-307 hands the worker pktbuf handles;
+// upe_worker.c gathers them per packet on the CPU).  ev: NULL, or four events recorded before the
+// size pass and after each pass (tools/ingress_gather_time.py).
+int ingress_gather(upe_gpu_ctx_t* c, const uint8_t* pool, size_t pool_bytes, size_t stride,
+                   const uint32_t* d_slot, size_t n, int mode, uint8_t* d_out, size_t out_bytes,
+                   uint64_t* d_desc, uint64_t* d_timestamp, uint32_t* d_ctrl,
+                   upe_ingress_info_t* d_info, void* stream, hipEvent_t* ev) {
+    if (!c) return fail("null context");
+    if (!d_info || (n && (!pool || !d_slot || !d_desc))) return fail("null buffer");
+    if (mode != UPE_INGRESS_REF && mode != UPE_INGRESS_WINDOW && mode != UPE_INGRESS_FULL)
+        return fail("unknown ingress mode");
+    if (stride % 16 != 0 || stride < 16 + UPE_FRAME_TAIL)
+        return fail("stride must be a multiple of 16 and at least 16 + UPE_FRAME_TAIL");
+    if (pool_bytes < stride || pool_bytes > (1ull << 36))
+        return fail("pool_bytes must be at least stride and at most 2^36");
+    if ((reinterpret_cast<uintptr_t>(pool) & 15u) != 0) return fail("pool must be 16-byte aligned");
+    if (mode == UPE_INGRESS_REF ? (d_out != nullptr || out_bytes != 0) : (n && !d_out))
+        return fail("d_out goes with WINDOW and FULL mode only");
+    if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0) return fail("d_out must be 16-byte aligned");
+    if (n > 0xFFFFFFFFull - UPE_INGRESS_BLOCK) return fail("n must fit in 32 bits");
+    if (mode == UPE_INGRESS_WINDOW && out_bytes / UPE_HDR_WINDOW < n)
+        return fail("d_out is smaller than n header windows");
+    DEV_SCOPE(c->device);
+    hipStream_t s = pick(c, stream);
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_info, 0, sizeof(upe_ingress_info_t), s));
+        HIP_TRY(hipMemsetAsync(&d_info->first_bad, 0xFF, sizeof(uint64_t), s));
+        HIP_TRY(hipMemsetAsync(&d_info->first_ctrl, 0xFF, sizeof(uint64_t), s));
+        return 0;
+    }
+    // the pool as the kernels address it: device memory, or pinned host memory through its mapping
+    hipPointerAttribute_t attr = {};
+    if (hipPointerGetAttributes(&attr, pool) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("pool is neither device memory nor pinned, mapped host memory");
+    }
+    const uint8_t* dpool = pool;
+    uintptr_t lo = reinterpret_cast<uintptr_t>(pool), hi = lo + pool_bytes;
+    if (attr.type == hipMemoryTypeHost) {
+        dpool = mapped(pool, "pool");
+        if (!dpool) return -1;
+        lo = reinterpret_cast<uintptr_t>(dpool), hi = lo + pool_bytes;
+    } else if (attr.type == hipMemoryTypeDevice) {
+        // where the caller's buffers end is not checked against the allocation, but d_out is kept
+        // out of all of it, as upe_gpu_egress_pack keeps it out of d_frames'
+        const uintptr_t end = alloc_end(pool, hi);
+        if (end > hi) hi = end;
+    } else {
+        return fail("pool is neither device memory nor pinned, mapped host memory");
+    }
+    if (d_out) {
+        const uintptr_t out = reinterpret_cast<uintptr_t>(d_out);
+        if (out < hi && lo < out + (out_bytes ? out_bytes : 1)) return fail("d_out overlaps the pool");
+    }
+    const size_t need = upe_ingress_scratch_bytes((uint32_t)n);
+    if (c->in_scratch.reserve(need, need + need / 4) != 0) return -1;
+    HIP_TRY(upe_ingress_launch(dpool, pool_bytes, stride, d_slot, (uint32_t)n, mode, d_out,
+                               out_bytes, d_desc, d_timestamp, d_ctrl, d_info, c->in_scratch.p, s,
+                               ev));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int upe_gpu_ingress_gather(upe_gpu_ctx_t* c, const uint8_t* pool, size_t pool_bytes, size_t stride,
+                           const uint32_t* d_slot, size_t n, int mode, uint8_t* d_out,
+                           size_t out_bytes, uint64_t* d_desc, uint64_t* d_timestamp,
+                           uint32_t* d_ctrl, upe_ingress_info_t* d_info, void* stream) {
+    return ingress_gather(c, pool, pool_bytes, stride, d_slot, n, mode, d_out, out_bytes, d_desc,
+                          d_timestamp, d_ctrl, d_info, stream, nullptr);
+}
+
+// Diagnostic (tools/ingress_gather_time.py; not in the header): one gather of n > 0 packets with
+// HIP events around each pass, then a plain hipMemcpyAsync of copy_bytes from copy_src to copy_dst
+// on the same stream (device to device, or host to device when copy_src is pinned host memory):
+// the yardstick for the bytes the gather moves.  ms[0..3] = the size, scan and write pass and that
+// copy.  Synchronous.
+int upe_gpu_ingress_gather_timed(upe_gpu_ctx_t* c, const uint8_t* pool, size_t pool_bytes,
+                                 size_t stride, const uint32_t* d_slot, size_t n, int mode,
+                                 uint8_t* d_out, size_t out_bytes, uint64_t* d_desc,
+                                 uint64_t* d_timestamp, uint32_t* d_ctrl,
+                                 upe_ingress_info_t* d_info, const uint8_t* copy_src,
+                                 uint8_t* copy_dst, size_t copy_bytes, void* stream, float* ms) {
+    if (!c || !ms || !copy_src || !copy_dst || n == 0)
+        return fail("null context, no output or an empty batch");
+    DEV_SCOPE(c->device);
+    hipStream_t s = pick(c, stream);
+    Events<6> ev;
+    if (ev.create() != 0 ||
+        ingress_gather(c, pool, pool_bytes, stride, d_slot, n, mode, d_out, out_bytes, d_desc,
+                       d_timestamp, d_ctrl, d_info, stream, ev.e) != 0)
+        return -1;
+    if (hipStreamSynchronize(s) != hipSuccess) return fail("waiting for the gather");
+    return ev.yardstick(copy_dst, copy_src, copy_bytes, hipMemcpyDefault, s, "the yardstick copy",
+                        ms);
+}
+
+}  // extern "C"

@@ -17,8 +17,8 @@
 // 64-bit global atomics (adds, one min, one max) on the context's histogram.  Adds, min and max of
 // integers commute, so the result does not depend on the order of lanes, waves or workgroups.
 // The histogram is kept as 64 copies a line apart, a workgroup's atomics going to copy
-// blockIdx % 64 (upe_latency.h): with all of a 1M-packet launch's 1024 workgroups on one line the
-// launch took 56 us, about 50 ns per workgroup queued behind the others.
+// blockIdx % 64 (UPE_LATENCY_REPLICAS, upe_ctx.h): with all of a 1M-packet launch's 1024
+// workgroups on one line the launch took 56 us, about 50 ns per workgroup queued behind the others.
 //
 // The sample's arithmetic is IEEE-754 double, each step rounded once: the conversion of the
 // 64-bit cycle count (its halves are exact doubles, the high one scaled by 2^32 exactly, their sum
@@ -27,9 +27,12 @@
 // saturates; the conversion is given a value in range in every case.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
-#include "../../include/upe_gpu.h"
-#include "upe_latency.h"
+#include <cfloat>
+#include <vector>
+
+#include "upe_ctx.h"
 
 namespace {
 
@@ -143,8 +146,9 @@ __global__ void __launch_bounds__(kThreads) upe_latency_record(
     }
 }
 
-}  // namespace
-
+// Queue the launch on `s`: the samples of packets [0, n) added to hist (the replicas, in device
+// memory, 128-byte aligned), with the arguments as latency_check has checked them; at most
+// max_grid > 0 workgroups, each walking the batch in strides of the grid.
 hipError_t upe_latency_launch(const uint64_t* timestamp, const uint32_t* verdict, uint32_t n,
                               uint64_t now, double cycles_per_ns, unsigned long long* hist,
                               uint32_t max_grid, hipStream_t s) {
@@ -154,3 +158,107 @@ hipError_t upe_latency_launch(const uint64_t* timestamp, const uint32_t* verdict
                        now, cycles_per_ns, hist);
     return hipGetLastError();
 }
+
+using namespace upe;
+
+constexpr size_t kLatWords = (size_t)UPE_LATENCY_REPLICAS * UPE_LATENCY_REPLICA_WORDS;
+
+int latency_check(upe_gpu_ctx_t* c, const uint64_t* d_timestamp, size_t n) {
+    if (!c) return fail("null context");
+    if (n && !d_timestamp) return fail("null buffer");
+    if (n > 0xFFFFFFFFull - UPE_LATENCY_BLOCK) return fail("n must fit in 32 bits");
+    if (!(c->cycles_per_ns > 0.0))
+        return fail("no calibration: upe_gpu_set_tsc has not succeeded on this context");
+    return 0;
+}
+
+// at most four workgroups per CU, each striding over the batch; UPE_GPU_GRID_CAP lowers it
+uint32_t latency_grid(const upe_gpu_ctx_t* c) {
+    const uint32_t g = 4u * (uint32_t)c->cus;
+    return c->grid_cap && c->grid_cap < g ? c->grid_cap : g;
+}
+
+}  // namespace
+
+int upe::latency_init_image(std::vector<unsigned long long>& img) {
+    upe_latency_hist_t h;
+    upe_latency_init(&h);
+    img.assign(kLatWords, 0);
+    for (size_t r = 0; r < UPE_LATENCY_REPLICAS; ++r)
+        memcpy(&img[r * UPE_LATENCY_REPLICA_WORDS], &h, sizeof h);
+    return 0;
+}
+
+extern "C" {
+
+// The worker's latency histogram (reference src/worker.c:120-122 ... 249-251 per packet,
+// src/latency.c:41-59).
+int upe_gpu_set_tsc(upe_gpu_ctx_t* c, double cycles_per_ns) {
+    if (!c) return fail("null context");
+    if (!(cycles_per_ns > 0.0 && cycles_per_ns <= DBL_MAX))
+        return fail("cycles_per_ns must be finite and > 0");
+    c->cycles_per_ns = cycles_per_ns;
+    return 0;
+}
+
+int upe_gpu_latency_record(upe_gpu_ctx_t* c, const uint64_t* d_timestamp,
+                           const uint32_t* d_verdict, size_t n, uint64_t now, void* stream) {
+    if (latency_check(c, d_timestamp, n) != 0) return -1;
+    if (n == 0) return 0;
+    DEV_SCOPE(c->device);
+    HIP_TRY(upe_latency_launch(d_timestamp, d_verdict, (uint32_t)n, now, c->cycles_per_ns,
+                               c->lat_hist.p, latency_grid(c), pick(c, stream)));
+    return 0;
+}
+
+// Diagnostic (tools/latency_time.py; not in the header): one upe_gpu_latency_record of n > 0
+// packets between two HIP events, then a plain hipMemcpyAsync of copy_bytes (device to device) on
+// the same stream between two more: the yardstick for the bytes the call reads.  ms[0] = the
+// launch, ms[1] = the copy.  Synchronous.
+int upe_gpu_latency_record_timed(upe_gpu_ctx_t* c, const uint64_t* d_timestamp,
+                                 const uint32_t* d_verdict, size_t n, uint64_t now,
+                                 const uint8_t* copy_src, uint8_t* copy_dst, size_t copy_bytes,
+                                 void* stream, float* ms) {
+    if (!ms || !copy_src || !copy_dst || n == 0) return fail("no output or an empty batch");
+    if (latency_check(c, d_timestamp, n) != 0) return -1;
+    DEV_SCOPE(c->device);
+    hipStream_t s = pick(c, stream);
+    Events<4> ev;
+    if (ev.create() != 0) return -1;
+    HIP_TRY(hipEventRecord(ev.e[0], s));
+    HIP_TRY(upe_latency_launch(d_timestamp, d_verdict, (uint32_t)n, now, c->cycles_per_ns,
+                               c->lat_hist.p, latency_grid(c), s));
+    HIP_TRY(hipEventRecord(ev.e[1], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return ev.yardstick(copy_dst, copy_src, copy_bytes, hipMemcpyDeviceToDevice, s,
+                        "the yardstick copy", ms);
+}
+
+int upe_gpu_get_latency(upe_gpu_ctx_t* c, upe_latency_hist_t* out) {
+    if (!c || !out) return fail("null argument");
+    DEV_SCOPE(c->device);
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<unsigned long long> img(kLatWords);
+    HIP_TRY(hipMemcpy(img.data(), c->lat_hist.p, kLatWords * sizeof(unsigned long long),
+                      hipMemcpyDeviceToHost));
+    upe_latency_init(out);
+    for (size_t r = 0; r < UPE_LATENCY_REPLICAS; ++r) {
+        upe_latency_hist_t h;
+        memcpy(&h, &img[r * UPE_LATENCY_REPLICA_WORDS], sizeof h);
+        upe_latency_merge(out, &h);
+    }
+    return 0;
+}
+
+int upe_gpu_reset_latency(upe_gpu_ctx_t* c) {
+    if (!c) return fail("null context");
+    DEV_SCOPE(c->device);
+    HIP_TRY(hipDeviceSynchronize());   // launches on any stream have added what they add
+    std::vector<unsigned long long> img;
+    latency_init_image(img);
+    HIP_TRY(hipMemcpy(c->lat_hist.p, img.data(), kLatWords * sizeof(unsigned long long),
+                      hipMemcpyHostToDevice));
+    return 0;
+}
+
+}  // extern "C"

@@ -50,6 +50,8 @@ struct upe_rule_image {
     bool tree_ok = false;
     std::vector<uint4> timg;
     upe::TreeImage t;
+    // (the type's name is the ABI's, upe_rule_image_t; its code is not exported)
+    UPE_INTERNAL ~upe_rule_image() = default;
 };
 
 namespace upe {
@@ -66,7 +68,7 @@ UPE_INTERNAL int cuckoo3_place(const std::vector<uint32_t>& key, uint32_t& bits,
 
 // The neighbour snapshot a context looks up in (NeighIndex, upe_gpu.hip): each family's slot
 // array and its placement.  Host memory only; an empty family keeps one zero slot (bits 0).
-struct NeighImage {
+struct UPE_INTERNAL NeighImage {
     std::vector<uint4> arp, ndp;
     uint32_t arp_bits = 0, arp_seed = 0, ndp_bits = 0, ndp_seed = 0;
 };

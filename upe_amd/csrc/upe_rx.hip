@@ -26,8 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/upe_gpu.h"
-#include "upe_rx.h"
+#include "upe_ctx.h"
 
 namespace {
 
@@ -354,12 +353,12 @@ __global__ void __launch_bounds__(kRxThreads) upe_rx_scatter(uint32_t* ring, con
 uint32_t tiles_of(uint32_t n) { return (uint32_t)(((uint64_t)n + kRxBlock - 1) / kRxBlock); }
 uint32_t stride_of(uint32_t tiles) { return (tiles + kScanPer - 1) / kScanPer * kScanPer; }
 
-}  // namespace
-
+// Bytes of scratch one dispatch of n packets over `rings` rings needs (n > 0).
 size_t upe_rx_scratch_bytes(uint32_t n, uint32_t rings) {
     return ((size_t)(rings + 2u) * stride_of(tiles_of(n)) + UPE_RX_RINGS_MAX) * sizeof(uint32_t);
 }
 
+// Queue the three passes on `s`, with the arguments as rx_dispatch has checked them.
 hipError_t upe_rx_launch(const uint8_t* frames, const uint64_t* desc, uint32_t n, uint32_t rings,
                          uint32_t rr, uint32_t* ring, uint32_t* flow_hash, uint32_t* index,
                          uint64_t* desc_out, uint64_t* counts, uint32_t* scratch, hipStream_t s,
@@ -383,3 +382,64 @@ hipError_t upe_rx_launch(const uint8_t* frames, const uint64_t* desc, uint32_t n
     if ((e = hipGetLastError()) != hipSuccess) return e;
     return ev ? hipEventRecord(ev[3], s) : hipSuccess;
 }
+
+using namespace upe;
+
+// The RX thread's dispatch (reference src/rx_pcap.c:19-25,67-80).  ev: NULL, or four events
+// recorded before the hash pass and after each pass (tools/rx_dispatch_time.py).
+int rx_dispatch(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc, size_t n,
+                uint32_t rings, uint32_t rr_start, uint32_t* d_ring, uint32_t* d_flow_hash,
+                uint32_t* d_index, uint64_t* d_desc_out, uint64_t* d_counts, void* stream,
+                hipEvent_t* ev) {
+    if (!c) return fail("null context");
+    if (rings == 0 || (rings & (rings - 1)) != 0 || rings > UPE_RX_RINGS_MAX)
+        return fail("rings must be a power of two between 1 and " +
+                    std::to_string(UPE_RX_RINGS_MAX));
+    if (!d_counts || (n && (!d_frames || !d_desc || !d_ring || !d_index)))
+        return fail("null buffer");
+    if (n > 0xFFFFFFFFull - UPE_RX_BLOCK) return fail("n must fit in 32 bits");
+    DEV_SCOPE(c->device);
+    hipStream_t s = pick(c, stream);
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_counts, 0, (rings + 1) * sizeof(uint64_t), s));
+        return 0;
+    }
+    const size_t need = upe_rx_scratch_bytes((uint32_t)n, rings);
+    if (c->rx_scratch.reserve(need, need + need / 4) != 0) return -1;
+    HIP_TRY(upe_rx_launch(d_frames, d_desc, (uint32_t)n, rings, rr_start & (rings - 1), d_ring,
+                          d_flow_hash, d_index, d_desc_out, d_counts,
+                          reinterpret_cast<uint32_t*>(c->rx_scratch.p), s, ev));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int upe_gpu_rx_dispatch(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc, size_t n,
+                        uint32_t rings, uint32_t rr_start, uint32_t* d_ring, uint32_t* d_flow_hash,
+                        uint32_t* d_index, uint64_t* d_desc_out, uint64_t* d_counts, void* stream) {
+    return rx_dispatch(c, d_frames, d_desc, n, rings, rr_start, d_ring, d_flow_hash, d_index,
+                       d_desc_out, d_counts, stream, nullptr);
+}
+
+// Diagnostic (tools/rx_dispatch_time.py; not in the header): one dispatch of n > 0 packets with
+// HIP events around each pass; ms[0..2] = the hash, scan and scatter pass.  Synchronous.
+int upe_gpu_rx_dispatch_timed(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_desc,
+                              size_t n, uint32_t rings, uint32_t rr_start, uint32_t* d_ring,
+                              uint32_t* d_flow_hash, uint32_t* d_index, uint64_t* d_desc_out,
+                              uint64_t* d_counts, void* stream, float* ms) {
+    if (!c || !ms || n == 0) return fail("null context, no output or an empty batch");
+    DEV_SCOPE(c->device);
+    Events<4> ev;
+    if (ev.create() != 0 ||
+        rx_dispatch(c, d_frames, d_desc, n, rings, rr_start, d_ring, d_flow_hash, d_index,
+                    d_desc_out, d_counts, stream, ev.e) != 0)
+        return -1;
+    HIP_TRY(hipEventSynchronize(ev.e[3]));
+    for (int k = 0; k < 3; ++k)
+        if (ev.elapsed(&ms[k], k, k + 1) != 0) return -1;
+    return 0;
+}
+
+}  // extern "C"
