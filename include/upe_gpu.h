@@ -257,6 +257,42 @@ int upe_gpu_rule_index_info(upe_gpu_ctx_t *ctx, upe_rule_index_info_t *info);
 int upe_rules_match_host(const upe_rule_t *rules, size_t count, const upe_flow_key_t *keys,
                          size_t n, int64_t *out, upe_rule_index_info_t *info);
 
+/* Flow keys on the device, apart from the classify launch (csrc/upe_keys.hip): the two reference
+ * entry points callers use on their own.  Both are read-only with respect to the context: the
+ * loaded table, rule_stats, the counters, the L1 state and upe_gpu_launch_info are untouched, and
+ * no launch is counted.  n == 0 is a successful no-op; a null context, a null buffer with n > 0
+ * or an n above 2^32 - 257 fails (-1, upe_gpu_last_error()) before anything is launched.
+ *
+ * parse_flow_key (src/parser.c:6-111; the RX thread's call, src/rx_pcap.c:71-72) over a resident
+ * batch ("Batch layout", the UPE_FRAME_TAIL rule of upe_gpu_process).  Frames are read only.
+ * Plain parse_flow_key, not the worker's control-packet handling: an ARP frame and an ICMPv6
+ * NS/NA both fail to parse (ethertype 0x0806; protocol 58).  Success: d_rc[i] = 0 and d_keys[i] =
+ * the 44 bytes the parser leaves in a key zeroed beforehand (an IPv4 key's union bytes 4-15 and
+ * the padding bytes 1-3 and 41-43 zero; addresses and ports in the reference's byte orders: IPv4
+ * host order in .v4, IPv6 wire bytes, ports host order).  Failure: d_rc[i] = -1 and 44 zero bytes,
+ * so ip_ver == 0 marks a failed parse when d_rc is NULL.  A byte at or past len never influences
+ * a key or a result.  Every byte of d_keys[0..n) is written.  Asynchronous on `stream` (NULL:
+ * the context's). */
+int upe_gpu_parse_keys(upe_gpu_ctx_t *ctx, const uint8_t *d_frames, const uint64_t *d_desc,
+                       size_t n, upe_flow_key_t *d_keys, int32_t *d_rc /* optional */,
+                       void *stream);
+
+/* rule_table_match (src/rule_table.c:163-176) over n keys on the device: d_rule[i] = the index,
+ * in the sorted rules[] the table was loaded or compiled from, of the first rule that matches
+ * d_keys[i], or -1: no rule matches, or ip_ver is neither 4 nor 6 (upe_rules_match_host's
+ * convention; the reference's match_rule, src/rule_table.c:76-91, would skip the address test
+ * for such a key, and parse_flow_key never produces one).  Of an IPv4 key's addresses only union
+ * bytes 0-3 are read; padding never is.  Whichever index the table's compiler chose (or was told
+ * to choose: UPE_GPU_TSS, UPE_GPU_TREE, UPE_GPU_TREE_BINTH) is the one that is probed.
+ * image == NULL: the context's loaded table; fails when the context holds no rules (none loaded
+ * since upe_gpu_open, or an empty table).  Asynchronous on `stream`.
+ * With an image (upe_rules_compile), a dry run before upe_gpu_reload_image: the image is uploaded
+ * beside the loaded table for the duration of the call, as a reload uploads it but without the
+ * swap, and is not consumed (it may be used again, and reloaded).  This form is synchronous: it
+ * returns once d_rule is written, and the device copy is gone by then. */
+int upe_gpu_match_keys(upe_gpu_ctx_t *ctx, const upe_rule_image_t *image /* NULL: loaded table */,
+                       const upe_flow_key_t *d_keys, size_t n, int32_t *d_rule, void *stream);
+
 /* Upload a snapshot of the neighbour tables' slot arrays (arpt->entries / ndpt->entries with
  * their power-of-two capacities).  Lookups probe exactly as arp_get_mac/ndp_get_mac do.
  * Either table may be NULL with capacity 0 (every lookup misses).  All or nothing: the new

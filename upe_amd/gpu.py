@@ -145,6 +145,8 @@ def _load() -> ctypes.CDLL:
         "upe_gpu_latency_record": (I, [P, P, P, SZ, ctypes.c_uint64, P]),
         "upe_gpu_get_latency": (I, [P, P]),
         "upe_gpu_reset_latency": (I, [P]),
+        "upe_gpu_parse_keys": (I, [P, P, P, SZ, P, P, P]),
+        "upe_gpu_match_keys": (I, [P, P, P, SZ, P, P]),
         "upe_gpu_process_segmented": (I, [P, P, P, P, SZ, P, SZ, P, SZ, ctypes.c_int64, P, P]),
         "upe_gpu_process_emit": (I, [P, P, P, P, P, SZ, P]),
         "upe_gpu_process_emit_tx": (I, [P, P, P, P, P, P, P, SZ, P]),
@@ -215,7 +217,8 @@ EXPORTED = ("upe_gpu_last_error", "upe_gpu_device_count", "upe_gpu_local_cpus", 
             "upe_tx_flush_packed", "upe_gpu_ingress_gather",
             "upe_latency_init", "upe_latency_record", "upe_latency_percentile",
             "upe_latency_merge", "upe_latency_record_batch", "upe_gpu_set_tsc",
-            "upe_gpu_latency_record", "upe_gpu_get_latency", "upe_gpu_reset_latency")
+            "upe_gpu_latency_record", "upe_gpu_get_latency", "upe_gpu_reset_latency",
+            "upe_gpu_parse_keys", "upe_gpu_match_keys")
 
 
 def _check(rc: int, what: str) -> None:
@@ -541,6 +544,25 @@ class GpuWorker:
 
     def reset_latency(self) -> None:
         _check(LIB.upe_gpu_reset_latency(self._ctx), "upe_gpu_reset_latency")
+
+    # ---- flow keys ----
+    def parse_keys(self, frames, desc, n: int, keys, rc=None, stream=None) -> None:
+        """upe_gpu_parse_keys: parse_flow_key of each packet of a resident batch (keys.parse_keys
+        is the same on the host).  Device buffers: keys (n FLOW_KEY_DTYPE records, 44 bytes each),
+        rc (n int32, or None); a failed parse leaves rc -1 and a zero key."""
+        _check(LIB.upe_gpu_parse_keys(self._ctx, _dev_ptr(frames) or None, _dev_ptr(desc) or None,
+                                      n, _dev_ptr(keys) or None, _dev_ptr(rc) or None,
+                                      stream or None), "upe_gpu_parse_keys")
+
+    def match_keys(self, keys, n: int, rule, image: "RuleImage | None" = None,
+                   stream=None) -> None:
+        """upe_gpu_match_keys: the sorted index of each key's first matching rule, or -1
+        (keys.match_keys is the same on the host).  Device buffers: keys (n FLOW_KEY_DTYPE
+        records), rule (n int32).  image: a RuleImage to match against instead of the loaded
+        table, which stays loaded (a dry run; synchronous)."""
+        _check(LIB.upe_gpu_match_keys(self._ctx, image.ptr if image is not None else None,
+                                      _dev_ptr(keys) or None, n, _dev_ptr(rule) or None,
+                                      stream or None), "upe_gpu_match_keys")
 
     def sync(self, stream=None) -> None:
         _check(LIB.upe_gpu_sync(self._ctx, stream or None), "upe_gpu_sync")
