@@ -257,6 +257,14 @@ int upe_gpu_rule_index_info(upe_gpu_ctx_t *ctx, upe_rule_index_info_t *info);
 int upe_rules_match_host(const upe_rule_t *rules, size_t count, const upe_flow_key_t *keys,
                          size_t n, int64_t *out, upe_rule_index_info_t *info);
 
+/* upe_gpu_resolve_keys' host twin (upe_host.c): arp_get_mac / ndp_get_mac over n keys, the
+ * reference's linear probe restated over the caller's slot arrays themselves (power-of-two
+ * capacities, or NULL with capacity 0: every lookup of that family misses) — no index is built.
+ * mac[i] in upe_gpu_resolve_keys' format.  No GPU needed.  0 / -1 (upe_host_last_error()). */
+int upe_neigh_lookup_host(const upe_arp_entry_t *arp, size_t arp_capacity,
+                          const upe_ndp_entry_t *ndp, size_t ndp_capacity,
+                          const upe_flow_key_t *keys, size_t n, uint64_t *mac);
+
 /* Flow keys on the device, apart from the classify launch (csrc/upe_keys.hip): the two reference
  * entry points callers use on their own.  Both are read-only with respect to the context: the
  * loaded table, rule_stats, the counters, the L1 state and upe_gpu_launch_info are untouched, and
@@ -302,6 +310,49 @@ int upe_gpu_match_keys(upe_gpu_ctx_t *ctx, const upe_rule_image_t *image /* NULL
  * device during the call, 16 bytes per ARP index slot and 32 per NDP index slot. */
 int upe_gpu_load_neigh(upe_gpu_ctx_t *ctx, const upe_arp_entry_t *arp, size_t arp_capacity,
                        const upe_ndp_entry_t *ndp, size_t ndp_capacity);
+
+/* The same load in two halves, as the rule reload has them: the snapshot's index is built where
+ * the tables change — the thread that runs arp_expire / ndp_expire — and the worker thread only
+ * uploads it between two bursts.
+ * upe_neigh_compile: the snapshot of the two slot arrays (upe_gpu_load_neigh's arguments, checked
+ * the same way: power-of-two capacities, a table wherever there is a capacity); host only (no
+ * context, no GPU), any thread; NULL on error (upe_gpu_last_error() on the calling thread) — a bad
+ * argument, or the index placement: at most three reachable IPv6 addresses may share one key of
+ * the index (fold_v6).  Equal tables give equal images.
+ * upe_gpu_load_neigh_image: upe_gpu_load_neigh() with that image — uploaded beside the previous
+ * snapshot and swapped in once it is whole; a call that fails (-1) keeps the previous snapshot.
+ * The image is not consumed.  upe_neigh_image_free: NULL is a no-op. */
+typedef struct upe_neigh_image upe_neigh_image_t;
+upe_neigh_image_t *upe_neigh_compile(const upe_arp_entry_t *arp, size_t arp_capacity,
+                                     const upe_ndp_entry_t *ndp, size_t ndp_capacity);
+int upe_gpu_load_neigh_image(upe_gpu_ctx_t *ctx, const upe_neigh_image_t *image);
+void upe_neigh_image_free(upe_neigh_image_t *image);
+
+/* arp_get_mac (src/arp_table.c:55-80) / ndp_get_mac (src/ndp_table.c:67-86) over n keys on the
+ * device (csrc/upe_neigh.hip): the next hop of d_keys[i].dst_ip by d_keys[i].ip_ver — 4: the ARP
+ * table, asked for union bytes 0-3 as a little-endian word (dst_ip.v4; bytes 4-15 are never read);
+ * 6: the NDP table, asked for the 16 bytes; anything else: not found.  d_mac[i] = the MAC's six
+ * bytes in bits 0-47 (byte 0 lowest: a memcpy of the MAC into a zeroed little-endian uint64_t)
+ * with bit 48 set, or exactly 0 when the address is not found.  Answers are those of the
+ * reference's probe over the slot arrays the snapshot was built from: an entry no probe reaches
+ * is not found, of one address in two slots the one the probe meets first answers, a stale
+ * address in an invalid slot is not found.  The table function alone: no L1 cache (the zero guard
+ * of src/worker.c:186 is the worker's; 0.0.0.0 and :: are ordinary addresses here), no TTL check,
+ * no rule; the counters, rule_stats, the L1 state and upe_gpu_launch_info are untouched and no
+ * launch is counted.
+ * image == NULL: the context's loaded snapshot.  Asynchronous on `stream` (NULL: the context's),
+ * one launch; the caller lets it finish (upe_gpu_sync) before the next upe_gpu_load_neigh or
+ * upe_gpu_load_neigh_image when the stream is one of its own.
+ * With an image (upe_neigh_compile), a dry run before upe_gpu_load_neigh_image: the image is
+ * uploaded beside the loaded snapshot for the duration of the call, without the swap, and is not
+ * consumed.  This form is synchronous: it returns once d_mac is written, and the device copy is
+ * gone by then.
+ * n == 0 launches nothing.  -1 (upe_gpu_last_error()) before any launch: a NULL context; NULL
+ * d_keys or d_mac with n > 0; d_keys not 4-byte or d_mac not 8-byte aligned; n above 2^32 - 257. */
+int upe_gpu_resolve_keys(upe_gpu_ctx_t *ctx,
+                         const upe_neigh_image_t *image /* NULL: the loaded snapshot */,
+                         const upe_flow_key_t *d_keys, size_t n, uint64_t *d_mac, void *stream);
+#define UPE_MAC_FOUND (1ull << 48) /* set in d_mac[i] / mac[i] on a hit */
 
 /* The TX port identity the worker reads from tx_ctx_t (include/tx.h:9-14): own MAC (source MAC of
  * forwarded frames, src/worker.c:199,229) and own IPv4 (ARP replies, src/worker.c:40). */

@@ -150,7 +150,8 @@ struct Events {
 };
 
 // The neighbour snapshot on the device (NeighIndex): one value, uploaded whole and then swapped
-// into the context (upe_gpu_load_neigh).
+// into the context (upe_gpu_load_neigh_image), or looked up in for one call and dropped
+// (upe_gpu_resolve_keys' dry run, upe_neigh.hip).
 struct NeighTable {
     DevBuf<uint4> arp, ndp;
     uint32_t arp_bits = 0, arp_seed = 0, ndp_bits = 0, ndp_seed = 0;

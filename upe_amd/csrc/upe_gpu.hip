@@ -77,6 +77,7 @@
 
 #include "upe_ctx.h"
 #include "upe_match.h"
+#include "upe_neigh_lookup.h"
 #include "upe_plan.h"
 
 using namespace upe;
@@ -184,16 +185,7 @@ struct DevState {
     unsigned long long* stats_idx;   // [kStatReps][nrules_pad][2] totals per sorted index
 };
 
-// Neighbour index (built by upe_gpu_load_neigh): the entries a reference probe reaches, placed
-// by three-choice cuckoo hashing, so that every key sits in one of its three candidate slots.
-//   ARP slot: uint4 {ip, mac0..3, mac4..5 | used << 16, 0}
-//   NDP slot: 2 x uint4 {ip words 0..3}, {mac0..3, mac4..5 | used << 16, 0, 0}
-struct NeighIndex {
-    const uint4* t;
-    uint32_t bits;   // log2(slots); 0 = empty
-    uint32_t seed;
-};
-
+// (NeighIndex, the neighbour index a launch looks up in: upe_neigh_lookup.h)
 struct Args {
     uint8_t* frames;
     const uint64_t* desc;
@@ -359,84 +351,8 @@ __device__ __forceinline__ void store16(uint4* p, uint4 v) { *p = v; }
 // device batches (C +12 us, B +6.5 us per 1M) and for host-memory batches (config B mapped 537
 // vs 666-680 Mpps in place, C 214 vs 319; profiles/r03/v5_host_nt_ab.txt).
 
-// ---- neighbour lookups (fold_v6: upe_dev.h) -------------------------------------------------
-__device__ __forceinline__ bool arp_slot_hit(const uint4& e, uint32_t ip) {
-    return ((e.z >> 16) & 1u) && e.x == ip;
-}
-__device__ __forceinline__ bool arp_lookup(const NeighIndex& x, uint32_t ip, uint32_t& lo,
-                                           uint32_t& hi) {
-    if (x.bits == 0) return false;
-    const uint4 e1 = x.t[slot1(ip, x.seed, x.bits)];
-    const uint4 e2 = x.t[slot2(ip, x.seed, x.bits)];
-    const uint4 e3 = x.t[slot3(ip, x.seed, x.bits)];
-    const bool h1 = arp_slot_hit(e1, ip), h2 = arp_slot_hit(e2, ip), h3 = arp_slot_hit(e3, ip);
-    const uint4 e = h1 ? e1 : h2 ? e2 : e3;
-    lo = e.y;
-    hi = e.z & 0xFFFFu;
-    return h1 || h2 || h3;
-}
-// The same lookup against an LDS copy of the slot array.
-__device__ __forceinline__ bool arp_lookup_lds(const uint4* t, uint32_t bits, uint32_t seed,
-                                               uint32_t ip, uint32_t& lo, uint32_t& hi) {
-    const uint4 e1 = t[slot1(ip, seed, bits)];
-    const uint4 e2 = t[slot2(ip, seed, bits)];
-    const uint4 e3 = t[slot3(ip, seed, bits)];
-    const bool h1 = arp_slot_hit(e1, ip), h2 = arp_slot_hit(e2, ip), h3 = arp_slot_hit(e3, ip);
-    const uint4 e = h1 ? e1 : h2 ? e2 : e3;
-    lo = e.y;
-    hi = e.z & 0xFFFFu;
-    return h1 || h2 || h3;
-}
-__device__ __forceinline__ bool ndp_slot_hit(const uint4& a, const uint4& m, const uint32_t ip[4]) {
-    return ((m.y >> 16) & 1u) && a.x == ip[0] && a.y == ip[1] && a.z == ip[2] && a.w == ip[3];
-}
-__device__ __forceinline__ bool ndp_lookup_lds(const uint4* t, uint32_t bits, uint32_t seed,
-                                               const uint32_t ip[4], uint32_t& lo, uint32_t& hi) {
-    const uint32_t k = fold_v6(ip);
-    const uint32_t t1 = slot1(k, seed, bits), t2 = slot2(k, seed, bits), t3 = slot3(k, seed, bits);
-    const uint4 a1 = t[2 * t1], m1 = t[2 * t1 + 1];
-    const uint4 a2 = t[2 * t2], m2 = t[2 * t2 + 1];
-    const uint4 a3 = t[2 * t3], m3 = t[2 * t3 + 1];
-    const bool h1 = ndp_slot_hit(a1, m1, ip), h2 = ndp_slot_hit(a2, m2, ip),
-               h3 = ndp_slot_hit(a3, m3, ip);
-    const uint4 m = h1 ? m1 : h2 ? m2 : m3;
-    lo = m.x;
-    hi = m.y & 0xFFFFu;
-    return h1 || h2 || h3;
-}
-__device__ __forceinline__ bool ndp_lookup(const NeighIndex& x, const uint32_t ip[4], uint32_t& lo,
-                                           uint32_t& hi) {
-    if (x.bits == 0) return false;
-    return ndp_lookup_lds(x.t, x.bits, x.seed, ip, lo, hi);
-}
-
-// Both families in one lookup: the IPv4 (ARP) and IPv6 (NDP) lanes of a wave issue their slot
-// loads together, so a mixed wave waits for one memory round trip, not one per family.
-__device__ __forceinline__ bool neigh_lookup(const NeighIndex& arp, const NeighIndex& ndp,
-                                             bool v6, const uint32_t d[4], uint32_t& lo,
-                                             uint32_t& hi) {
-    const uint4* t = v6 ? ndp.t : arp.t;
-    const uint32_t bits = v6 ? ndp.bits : arp.bits;
-    const uint32_t seed = v6 ? ndp.seed : arp.seed;
-    if (bits == 0) return false;
-    const uint32_t k = v6 ? fold_v6(d) : d[0];
-    const uint32_t t1 = slot1(k, seed, bits), t2 = slot2(k, seed, bits), t3 = slot3(k, seed, bits);
-    const uint32_t sh = v6 ? 1u : 0u;   // an NDP slot is two uint4: address, then MAC
-    const uint4 a1 = t[t1 << sh], a2 = t[t2 << sh], a3 = t[t3 << sh];
-    uint4 m1 = a1, m2 = a2, m3 = a3;
-    if (v6) {
-        m1 = t[2 * t1 + 1];
-        m2 = t[2 * t2 + 1];
-        m3 = t[2 * t3 + 1];
-    }
-    const bool h1 = v6 ? ndp_slot_hit(a1, m1, d) : arp_slot_hit(a1, d[0]);
-    const bool h2 = v6 ? ndp_slot_hit(a2, m2, d) : arp_slot_hit(a2, d[0]);
-    const bool h3 = v6 ? ndp_slot_hit(a3, m3, d) : arp_slot_hit(a3, d[0]);
-    const uint4 e = h1 ? (v6 ? m1 : a1) : h2 ? (v6 ? m2 : a2) : (v6 ? m3 : a3);
-    lo = v6 ? e.x : e.y;
-    hi = (v6 ? e.y : e.z) & 0xFFFFu;
-    return h1 || h2 || h3;
-}
+// (the neighbour lookups, arp_lookup ... neigh_lookup: upe_neigh_lookup.h, shared with
+// upe_neigh.hip)
 
 // Does each L1 entry agree with the table?  (ARP: an entry for 0.0.0.0 is never consulted,
 // src/worker.c:186, so it always "agrees".)
@@ -2399,16 +2315,19 @@ extern "C" int upe_gpu_rule_index_info(upe_gpu_ctx_t* c, upe_rule_index_info_t* 
 int upe_gpu_load_neigh(upe_gpu_ctx_t* c, const upe_arp_entry_t* arp, size_t arp_capacity,
                        const upe_ndp_entry_t* ndp, size_t ndp_capacity) {
     if (!c) return fail("null context");
-    auto pow2 = [](size_t x) { return x == 0 || (x & (x - 1)) == 0; };
-    if (!pow2(arp_capacity) || !pow2(ndp_capacity))
-        return fail("neighbour table capacity must be a power of two (arp_table_init)");
-    if ((arp_capacity && !arp) || (ndp_capacity && !ndp)) return fail("null table");
-    if (arp_capacity > (1u << 30) || ndp_capacity > (1u << 30)) return fail("table too large");
+    upe_neigh_image image;
+    if (compile_neigh(arp, arp_capacity, ndp, ndp_capacity, image.im) != 0) return -1;
+    return upe_gpu_load_neigh_image(c, &image);
+}
+
+// The second half of the same load, for a snapshot compiled beforehand (upe_neigh_compile, any
+// thread): the upload, the swap, and the L1 entries' agreement with the new tables.
+int upe_gpu_load_neigh_image(upe_gpu_ctx_t* c, const upe_neigh_image_t* image) {
+    if (!c) return fail("null context");
+    if (!image) return fail("null neighbour image");
     DEV_SCOPE(c->device);
-    NeighImage im;
     NeighTable next;   // dropped on an error return
-    if (build_neigh_image(arp, arp_capacity, ndp, ndp_capacity, im) != 0 || next.upload(im) != 0)
-        return -1;
+    if (next.upload(image->im) != 0) return -1;
     // the last batch's L1 outcome into the starting state before the tables change
     if (c->st && l1_sync(c) != 0) return -1;
     if (c->last_stream) HIP_TRY(hipStreamSynchronize(c->last_stream));

@@ -17,6 +17,9 @@
  *                       src/worker.c:162-244 as bytes.
  *   upe_latency_*       the worker's latency histogram (reference include/latency.h:21-40,
  *                       src/latency.c:35-90) and the host equivalent of upe_gpu_latency_record.
+ *   upe_neigh_lookup_host  arp_get_mac / ndp_get_mac (src/arp_table.c:55-80,
+ *                       src/ndp_table.c:67-86) per flow key over the slot arrays: the host
+ *                       equivalent of upe_gpu_resolve_keys.
  */
 #define _GNU_SOURCE
 #include <arpa/inet.h>
@@ -438,6 +441,55 @@ int upe_tx_flush_packed(const uint8_t *h_out, const uint64_t *h_out_desc,
 }
 
 int upe_gpu_hdr_layout(void) { return UPE_HDR_LAYOUT; }
+
+/* ---- neighbour lookup ------------------------------------------------------------------- */
+
+static uint32_t ld_le32(const uint8_t *p) {
+    return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+}
+
+/* a hit's MAC in upe_gpu_resolve_keys' format */
+static uint64_t mac_found(const uint8_t mac[6]) {
+    uint64_t v = UPE_MAC_FOUND;
+    for (int j = 0; j < 6; j++) v |= (uint64_t)mac[j] << (8 * j);
+    return v;
+}
+
+/* src/arp_table.c:55-80: from the address's low bits, the first valid entry of the address;
+ * nothing past the first invalid slot */
+static uint64_t arp_probe(const upe_arp_entry_t *t, size_t cap, uint32_t ip) {
+    for (size_t i = 0, s = ip & (cap - 1); i < cap; i++, s = (s + 1) & (cap - 1)) {
+        if (!t[s].valid) break;
+        if (t[s].ip == ip) return mac_found(t[s].mac);
+    }
+    return 0;
+}
+
+/* src/ndp_table.c:67-86, from hash_ipv6 (:6-17): the XOR of the four words as the bytes lie */
+static uint64_t ndp_probe(const upe_ndp_entry_t *t, size_t cap, const uint8_t ip[16]) {
+    const size_t home = ld_le32(ip) ^ ld_le32(ip + 4) ^ ld_le32(ip + 8) ^ ld_le32(ip + 12);
+    for (size_t i = 0, s = home & (cap - 1); i < cap; i++, s = (s + 1) & (cap - 1)) {
+        if (!t[s].valid) break;
+        if (memcmp(t[s].ip, ip, 16) == 0) return mac_found(t[s].mac);
+    }
+    return 0;
+}
+
+int upe_neigh_lookup_host(const upe_arp_entry_t *arp, size_t arp_capacity,
+                          const upe_ndp_entry_t *ndp, size_t ndp_capacity,
+                          const upe_flow_key_t *keys, size_t n, uint64_t *mac) {
+    if ((arp_capacity & (arp_capacity - 1)) != 0 || (ndp_capacity & (ndp_capacity - 1)) != 0)
+        return host_fail("upe_neigh_lookup_host: capacity must be a power of two%.0d%s", 0, "");
+    if ((arp_capacity && !arp) || (ndp_capacity && !ndp) || (n && (!keys || !mac)))
+        return host_fail("upe_neigh_lookup_host: null argument%.0d%s", 0, "");
+    for (size_t k = 0; k < n; k++) {
+        const uint8_t *d = keys[k].dst_ip.v6;
+        mac[k] = keys[k].ip_ver == 4 ? arp_probe(arp, arp_capacity, ld_le32(d))
+               : keys[k].ip_ver == 6 ? ndp_probe(ndp, ndp_capacity, d)
+                                     : 0;
+    }
+    return 0;
+}
 
 /* ---- latency histogram ------------------------------------------------------------------ */
 

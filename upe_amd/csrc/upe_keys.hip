@@ -7,14 +7,9 @@
 // Both kernels: one key per lane, workgroups of 256 threads walking 256-key tiles a grid apart, no
 // state between keys, no atomics; neither touches anything of the context's but the rule table.
 //
-// Keys are 44-byte records (upe_flow_key_t, 11 words), so a lane's record is neither 16-byte
-// aligned nor a multiple of 16 bytes, and 64 lanes each storing their own words put 64 x 4 bytes
-// 44 bytes apart with every store instruction (eleven of them, each touching the wave's 22 lines).
-// A tile's 256 records go through LDS instead: a lane writes (reads) its record's words at word
-// 11 * lane + j (an odd stride: 64 lanes on 64 different banks), and the workgroup stores (loads)
-// the tile's 2816 words row by row, 256 consecutive words per instruction — every wave
-// instruction moves 256 contiguous bytes, whatever the alignment of the caller's array, and a
-// ragged last tile is a bound on the word index.
+// Keys are 44-byte records, so a tile's 256 records move between the caller's array and LDS row
+// by row, 256 contiguous words per instruction, and a lane takes its own record from LDS at an
+// odd stride (upe_key_tile.h, shared with upe_neigh.hip).
 //
 // upe_parse_keys reads a frame's first 96 bytes as 16-byte loads, only the chunks that begin below
 // len (the batch layout keeps UPE_FRAME_TAIL bytes readable behind every frame start), and clears
@@ -32,20 +27,10 @@
 #include <stdint.h>
 
 #include "upe_ctx.h"
+#include "upe_key_tile.h"
 #include "upe_match.h"
 
 namespace {
-
-constexpr uint32_t kThreads = 256;   // keys per tile
-constexpr uint32_t kKeyWords = 11;   // of a upe_flow_key_t
-static_assert(sizeof(upe_flow_key_t) == kKeyWords * sizeof(uint32_t), "flow key words");
-static_assert(offsetof(upe_flow_key_t, src_ip) == 4 && offsetof(upe_flow_key_t, dst_ip) == 20 &&
-                  offsetof(upe_flow_key_t, src_port) == 36 &&
-                  offsetof(upe_flow_key_t, dst_port) == 38 &&
-                  offsetof(upe_flow_key_t, protocol) == 40,
-              "flow key layout");
-// n + kThreads must not wrap (a tile's last lane index), and a tile index times kThreads neither
-constexpr size_t kMaxKeys = 0xFFFFFFFFull - kThreads;
 
 // A flow key in registers.  Record words: 0 ip_ver (bytes 1-3 padding), 1-4 src_ip, 5-8 dst_ip,
 // 9 src_port | dst_port << 16, 10 protocol (bytes 41-43 padding).
@@ -77,25 +62,6 @@ __device__ __forceinline__ Key key_from_words(const uint32_t (&w)[kKeyWords]) {
     k.dport = w[9] >> 16;
     k.proto = w[10] & 0xFFu;
     return k;
-}
-
-// A tile's records between LDS and the caller's array (see the top of the file).  base: the
-// tile's first word in the array; words: the array's.
-__device__ __forceinline__ void tile_store(uint32_t* g, const uint32_t* lds, size_t base,
-                                           size_t words, uint32_t tid) {
-#pragma unroll
-    for (uint32_t j = 0; j < kKeyWords; ++j) {
-        const uint32_t k = j * kThreads + tid;   // < kKeyWords * kThreads
-        if (base + k < words) g[base + k] = lds[k];
-    }
-}
-__device__ __forceinline__ void tile_load(uint32_t* lds, const uint32_t* g, size_t base,
-                                          size_t words, uint32_t tid) {
-#pragma unroll
-    for (uint32_t j = 0; j < kKeyWords; ++j) {
-        const uint32_t k = j * kThreads + tid;
-        lds[k] = base + k < words ? g[base + k] : 0u;
-    }
 }
 
 __device__ __forceinline__ uint32_t byte_of(uint32_t w, int k) { return (w >> (8 * k)) & 0xFFu; }
@@ -304,14 +270,8 @@ MatchKind match_kind(const DeviceTable& t) {
          : t.tree_ok ? M_TREE : t.fam_all ? M_WHOLE : M_FAM;
 }
 
-// at most eight workgroups (32 waves) per CU, each striding over the tiles; UPE_GPU_GRID_CAP
-// lowers it
-uint32_t keys_grid(const upe_gpu_ctx_t* c, size_t n) {
-    const uint32_t tiles = (uint32_t)((n + kThreads - 1) / kThreads);
-    uint32_t g = 8u * (uint32_t)c->cus;
-    if (c->grid_cap && c->grid_cap < g) g = c->grid_cap;
-    return tiles < g ? tiles : g;
-}
+// (key_grid: upe_key_tile.h)
+uint32_t keys_grid(const upe_gpu_ctx_t* c, size_t n) { return key_grid(c->cus, c->grid_cap, n); }
 
 int keys_check(const upe_gpu_ctx_t* c, size_t n) {
     if (!c) return fail("null context");

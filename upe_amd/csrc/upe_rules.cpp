@@ -1,7 +1,8 @@
 // upe_rules.cpp — the rule compiler of libupe_gpu: rule_t tables -> the images the classify
 // kernels read (upe_dev.h): the RuleV4 / RuleV6 words, the family lists, the tuple-space index,
 // the decision-tree forest; and the host walk of the tree (upe_rules_match_host).  Also the
-// neighbour snapshot upe_gpu_load_neigh uploads (build_neigh_image).  Plain C++, host memory
+// neighbour snapshot upe_gpu_load_neigh uploads (build_neigh_image; upe_neigh_compile hands it
+// out as a value, as upe_rules_compile hands out the rule image).  Plain C++, host memory
 // only: no context, no GPU, any thread.  tools/rules_san.cpp and tools/neigh_san.cpp run it under
 // the host sanitizers (`make rules-san`, `make neigh-san`).
 #include "upe_rules.h"
@@ -145,6 +146,17 @@ int build_neigh_image(const upe_arp_entry_t* arp, size_t arp_cap, const upe_ndp_
     if (im.arp.empty()) im.arp.push_back(make_uint4(0, 0, 0, 0));   // keep a valid allocation
     if (im.ndp.empty()) im.ndp.resize(2, make_uint4(0, 0, 0, 0));
     return 0;
+}
+
+// (upe_rules.h)
+int compile_neigh(const upe_arp_entry_t* arp, size_t arp_cap, const upe_ndp_entry_t* ndp,
+                  size_t ndp_cap, NeighImage& im) {
+    auto pow2 = [](size_t x) { return x == 0 || (x & (x - 1)) == 0; };
+    if (!pow2(arp_cap) || !pow2(ndp_cap))
+        return fail("neighbour table capacity must be a power of two (arp_table_init)");
+    if ((arp_cap && !arp) || (ndp_cap && !ndp)) return fail("null table");
+    if (arp_cap > (1u << 30) || ndp_cap > (1u << 30)) return fail("table too large");
+    return build_neigh_image(arp, arp_cap, ndp, ndp_cap, im);
 }
 
 }  // namespace upe
@@ -1045,6 +1057,27 @@ extern "C" upe_rule_image_t* upe_rules_compile(const upe_rule_t* rules, size_t c
 }
 
 extern "C" void upe_rules_image_free(upe_rule_image_t* im) { delete im; }
+
+// The neighbour snapshot the same way: upe_gpu_load_neigh's build, apart from any context.
+// (upe_neigh_image is a hidden type, as the NeighImage it holds; g++ would hide a function that
+// names it along with it, so the two entry points say that they are exported.)
+#define UPE_EXPORT __attribute__((visibility("default")))
+extern "C" UPE_EXPORT upe_neigh_image_t* upe_neigh_compile(const upe_arp_entry_t* arp, size_t arp_capacity,
+                                                const upe_ndp_entry_t* ndp, size_t ndp_capacity) {
+    try {
+        auto* im = new upe_neigh_image;
+        if (compile_neigh(arp, arp_capacity, ndp, ndp_capacity, im->im) != 0) {
+            delete im;
+            return nullptr;
+        }
+        return im;
+    } catch (const std::bad_alloc&) {
+        fail("out of memory (neighbour image)");
+        return nullptr;
+    }
+}
+
+extern "C" UPE_EXPORT void upe_neigh_image_free(upe_neigh_image_t* im) { delete im; }
 
 // (diagnostic, not part of the ABI) the same, and per key and tree of its family (first 16):
 // levels walked (prof_depth[16 * i + t]) and leaf entries read (prof_steps[16 * i + t])

@@ -1,8 +1,9 @@
 // upe_rules.h — the rule compiler (upe_rules.cpp, plain C++: no GPU, any thread): what
 // upe_gpu.hip installs into a context (struct upe_rule_image, build_image) and the neighbour
 // snapshot upe_gpu_load_neigh uploads (NeighImage, build_neigh_image, with the cuckoo placement
-// it shares with the compiler).  The extern "C" entry points of the compiler
-// (upe_rules_compile, upe_rules_image_free, upe_rules_match_host) are in include/upe_gpu.h.
+// it shares with the compiler; struct upe_neigh_image).  The extern "C" entry points of the
+// compiler (upe_rules_compile, upe_rules_image_free, upe_rules_match_host, upe_neigh_compile,
+// upe_neigh_image_free) are in include/upe_gpu.h.
 #ifndef UPE_RULES_H
 #define UPE_RULES_H
 
@@ -78,6 +79,20 @@ struct UPE_INTERNAL NeighImage {
 UPE_INTERNAL int build_neigh_image(const upe_arp_entry_t* arp, size_t arp_cap,
                                    const upe_ndp_entry_t* ndp, size_t ndp_cap, NeighImage& im);
 
+// upe_gpu_load_neigh's and upe_neigh_compile's arguments checked (power-of-two capacities of at
+// most 2^30 slots, a table wherever there is a capacity), then build_neigh_image.  0, or -1
+// (upe_gpu_last_error()).
+UPE_INTERNAL int compile_neigh(const upe_arp_entry_t* arp, size_t arp_cap,
+                               const upe_ndp_entry_t* ndp, size_t ndp_cap, NeighImage& im);
+
 }  // namespace upe
+
+// The compiled snapshot as the ABI hands it out (upe_neigh_compile): built apart from any
+// context, as a upe_rule_image is, so that the thread that expires the neighbour tables can build
+// it and a worker only uploads it (upe_gpu_load_neigh_image).  Host memory only.
+// (the type's name is the ABI's, upe_neigh_image_t; its code is not exported)
+struct UPE_INTERNAL upe_neigh_image {
+    upe::NeighImage im;
+};
 
 #endif  // UPE_RULES_H

@@ -147,6 +147,10 @@ def _load() -> ctypes.CDLL:
         "upe_gpu_reset_latency": (I, [P]),
         "upe_gpu_parse_keys": (I, [P, P, P, SZ, P, P, P]),
         "upe_gpu_match_keys": (I, [P, P, P, SZ, P, P]),
+        "upe_neigh_compile": (P, [P, SZ, P, SZ]),
+        "upe_neigh_image_free": (None, [P]),
+        "upe_gpu_load_neigh_image": (I, [P, P]),
+        "upe_gpu_resolve_keys": (I, [P, P, P, SZ, P, P]),
         "upe_gpu_process_segmented": (I, [P, P, P, P, SZ, P, SZ, P, SZ, ctypes.c_int64, P, P]),
         "upe_gpu_process_emit": (I, [P, P, P, P, P, SZ, P]),
         "upe_gpu_process_emit_tx": (I, [P, P, P, P, P, P, P, SZ, P]),
@@ -172,6 +176,7 @@ def _load() -> ctypes.CDLL:
     sig.update({
         "upe_rules_load_ini": (I, [ctypes.c_char_p, P, SZ, P]),
         "upe_rules_match_host": (I, [P, SZ, P, SZ, P, P]),
+        "upe_neigh_lookup_host": (I, [P, SZ, P, SZ, P, SZ, P]),
         "upe_pcap_read": (I, [ctypes.c_char_p, P, SZ, P, SZ, P]),
         "upe_host_last_error": (ctypes.c_char_p, []),
         "upe_latency_init": (None, [P]),
@@ -218,7 +223,9 @@ EXPORTED = ("upe_gpu_last_error", "upe_gpu_device_count", "upe_gpu_local_cpus", 
             "upe_latency_init", "upe_latency_record", "upe_latency_percentile",
             "upe_latency_merge", "upe_latency_record_batch", "upe_gpu_set_tsc",
             "upe_gpu_latency_record", "upe_gpu_get_latency", "upe_gpu_reset_latency",
-            "upe_gpu_parse_keys", "upe_gpu_match_keys")
+            "upe_gpu_parse_keys", "upe_gpu_match_keys",
+            "upe_neigh_compile", "upe_neigh_image_free", "upe_gpu_load_neigh_image",
+            "upe_gpu_resolve_keys", "upe_neigh_lookup_host")
 
 
 def _check(rc: int, what: str) -> None:
@@ -337,6 +344,11 @@ class GpuWorker:
         _check(LIB.upe_gpu_load_neigh(self._ctx, _np_ptr(a) if len(a) else None, len(a),
                                       _np_ptr(b) if len(b) else None, len(b)),
                "upe_gpu_load_neigh")
+
+    def load_neigh_image(self, image: "NeighImage") -> None:
+        """upe_gpu_load_neigh_image: load_neigh with a snapshot compiled beforehand (NeighImage,
+        e.g. on another thread); the image is not consumed."""
+        _check(LIB.upe_gpu_load_neigh_image(self._ctx, image.ptr), "upe_gpu_load_neigh_image")
 
     def set_port(self, eth_addr: bytes, ip4_addr: int) -> None:
         mac = np.frombuffer(bytes(eth_addr), np.uint8).copy()
@@ -564,6 +576,17 @@ class GpuWorker:
                                       _dev_ptr(keys) or None, n, _dev_ptr(rule) or None,
                                       stream or None), "upe_gpu_match_keys")
 
+    def resolve_keys(self, keys, n: int, mac, image: "NeighImage | None" = None,
+                     stream=None) -> None:
+        """upe_gpu_resolve_keys: arp_get_mac / ndp_get_mac of each key's dst_ip by its ip_ver
+        (neigh.resolve_keys is the same on the host).  Device buffers: keys (n FLOW_KEY_DTYPE
+        records), mac (n uint64: the MAC in bits 0-47 with bit 48 set, or 0).  image: a NeighImage
+        to look up in instead of the loaded snapshot, which stays loaded (a dry run;
+        synchronous)."""
+        _check(LIB.upe_gpu_resolve_keys(self._ctx, image.ptr if image is not None else None,
+                                        _dev_ptr(keys) or None, n, _dev_ptr(mac) or None,
+                                        stream or None), "upe_gpu_resolve_keys")
+
     def sync(self, stream=None) -> None:
         _check(LIB.upe_gpu_sync(self._ctx, stream or None), "upe_gpu_sync")
 
@@ -680,6 +703,26 @@ def rules_match_host(rules_sorted: np.ndarray, keys: np.ndarray):
                                     _np_ptr(out) if len(k) else None, _np_ptr(info)),
            "upe_rules_match_host")
     return out, info[0]
+
+
+def _neigh_tables(arp, ndp):
+    a = np.ascontiguousarray(arp if arp is not None else np.zeros(0, ARP_DTYPE), ARP_DTYPE)
+    b = np.ascontiguousarray(ndp if ndp is not None else np.zeros(0, NDP_DTYPE), NDP_DTYPE)
+    return a, b
+
+
+def neigh_lookup_host(arp, ndp, keys: np.ndarray) -> np.ndarray:
+    """upe_neigh_lookup_host: arp_get_mac / ndp_get_mac of each key (FLOW_KEY_DTYPE) by the
+    reference's probe over the slot arrays; uint64 per key in upe_gpu_resolve_keys' format."""
+    a, b = _neigh_tables(arp, ndp)
+    k = np.ascontiguousarray(keys, dtype=FLOW_KEY_DTYPE)
+    out = np.full(len(k), 0xA7A7A7A7A7A7A7A7, np.uint64)
+    if LIB.upe_neigh_lookup_host(_np_ptr(a) if len(a) else None, len(a),
+                                 _np_ptr(b) if len(b) else None, len(b),
+                                 _np_ptr(k) if len(k) else None, len(k),
+                                 _np_ptr(out) if len(k) else None) != 0:
+        raise UpeGpuError(f"upe_neigh_lookup_host: {LIB.upe_host_last_error().decode()}")
+    return out
 
 
 def pcap_read(path: str):
@@ -854,6 +897,27 @@ class RuleImage:
     def free(self) -> None:
         if self.ptr:
             LIB.upe_rules_image_free(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        self.free()
+
+
+class NeighImage:
+    """upe_neigh_compile: the neighbour snapshot of two slot arrays compiled for the GPU path on
+    the host, with no context or GPU (where the tables change: after arp_expire / ndp_expire);
+    free() (or garbage collection) releases it."""
+
+    def __init__(self, arp: np.ndarray | None, ndp: np.ndarray | None):
+        a, b = _neigh_tables(arp, ndp)
+        self.ptr = LIB.upe_neigh_compile(_np_ptr(a) if len(a) else None, len(a),
+                                         _np_ptr(b) if len(b) else None, len(b))
+        if not self.ptr:
+            raise UpeGpuError(f"upe_neigh_compile: {LIB.upe_gpu_last_error().decode()}")
+
+    def free(self) -> None:
+        if self.ptr:
+            LIB.upe_neigh_image_free(self.ptr)
             self.ptr = None
 
     def __del__(self):

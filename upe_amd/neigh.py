@@ -1,0 +1,73 @@
+"""arp_get_mac and ndp_get_mac restated on the host with numpy, over arrays of flow keys (reference
+src/arp_table.c:55-80, src/ndp_table.c:67-86 from hash_ipv6 :6-17).  This is the expected value of
+upe_gpu_resolve_keys and upe_neigh_lookup_host in the tests and the host side of
+tools/resolve_keys_time.py.  It needs no GPU and no library: the probe is written straight from the
+reference's statements, over the slot arrays themselves — no index is built.
+
+Every key probes at once: step i looks at slot (home + i) & (capacity - 1) of the keys still
+probing; a key leaves with the slot's MAC where the slot is valid and holds its address, and with
+nothing where the slot is invalid.  After `capacity` steps whoever is left has seen every slot."""
+from __future__ import annotations
+
+import numpy as np
+
+from .layout import ARP_DTYPE, FLOW_KEY_DTYPE, NDP_DTYPE
+
+MAC_FOUND = 1 << 48   # UPE_MAC_FOUND (include/upe_gpu.h)
+
+
+def _mac_words(mac: np.ndarray) -> np.ndarray:
+    """(slots, 6) MAC bytes -> the answer of a hit: byte 0 lowest, bit 48 set."""
+    out = np.full(len(mac), MAC_FOUND, np.uint64)
+    for j in range(6):
+        out |= mac[:, j].astype(np.uint64) << np.uint64(8 * j)
+    return out
+
+
+def _probe(home: np.ndarray, addr: np.ndarray, slot_addr: np.ndarray, valid: np.ndarray,
+           answer: np.ndarray) -> np.ndarray:
+    """home: (m,) starting slots before masking; addr: (m, w) addresses asked for; slot_addr:
+    (capacity, w), valid: (capacity,) bool, answer: (capacity,) uint64 per slot."""
+    out = np.zeros(len(home), np.uint64)
+    cap = len(valid)
+    if cap == 0 or len(home) == 0:
+        return out
+    mask = np.uint64(cap - 1)
+    live = np.arange(len(home))
+    cur = home.astype(np.uint64) & mask
+    for _ in range(cap):
+        s = cur.astype(np.int64)
+        ok = valid[s]
+        hit = ok & (slot_addr[s] == addr[live]).all(axis=1)
+        out[live[hit]] = answer[s[hit]]
+        go = ok & ~hit
+        live, cur = live[go], (cur[go] + np.uint64(1)) & mask
+        if live.size == 0:
+            break
+    return out
+
+
+def resolve_keys(arp, ndp, keys) -> np.ndarray:
+    """uint64 per key (FLOW_KEY_DTYPE): ip_ver 4 -> arp_get_mac(dst_ip.v4), the union's bytes 0-3
+    as a little-endian word; 6 -> ndp_get_mac(dst_ip.v6); anything else -> not found.  A hit is
+    the six MAC bytes in bits 0-47 (byte 0 lowest) with bit 48 set, a miss exactly 0.  arp / ndp:
+    the slot arrays (ARP_DTYPE / NDP_DTYPE, power-of-two lengths), or None / empty."""
+    arp = np.zeros(0, ARP_DTYPE) if arp is None else np.asarray(arp, ARP_DTYPE)
+    ndp = np.zeros(0, NDP_DTYPE) if ndp is None else np.asarray(ndp, NDP_DTYPE)
+    keys = np.asarray(keys, FLOW_KEY_DTYPE).ravel()
+    for t in (arp, ndp):
+        assert len(t) & (len(t) - 1) == 0, "capacity must be a power of two (arp_table_init)"
+    out = np.zeros(len(keys), np.uint64)
+    dst = np.ascontiguousarray(keys["dst_ip"]).reshape(-1, 16)
+    words = dst.view("<u4").reshape(-1, 4)
+    is4, is6 = keys["ip_ver"] == 4, keys["ip_ver"] == 6
+    # arp_get_mac: idx = ip & (capacity - 1)
+    ip = words[is4, 0]
+    out[is4] = _probe(ip, ip[:, None], np.ascontiguousarray(arp["ip"])[:, None],
+                      arp["valid"] != 0, _mac_words(arp["mac"]))
+    # ndp_get_mac: idx = hash_ipv6 = the XOR of the four words as the bytes lie, & (capacity - 1)
+    w6 = words[is6]
+    home = w6[:, 0] ^ w6[:, 1] ^ w6[:, 2] ^ w6[:, 3] if len(w6) else np.zeros(0, np.uint32)
+    slot_words = np.ascontiguousarray(ndp["ip"]).reshape(-1, 16).view("<u4").reshape(-1, 4)
+    out[is6] = _probe(home, w6, slot_words, ndp["valid"] != 0, _mac_words(ndp["mac"]))
+    return out
