@@ -904,6 +904,85 @@ int upe_gpu_process_segmented(upe_gpu_ctx_t *ctx, uint8_t *d_frames, const uint6
                               size_t arp_capacity, upe_ndp_entry_t *ndp, size_t ndp_capacity,
                               int64_t now, size_t *n_writes, void *stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Control writes: what a resident batch's control packets teach, as records                   */
+/* ------------------------------------------------------------------------------------------ */
+/* The table writes of handle_control_packet (reference src/worker.c:23-104) for a batch resident
+ * in GPU memory ("Batch layout", the UPE_FRAME_TAIL rule of upe_gpu_process), without the host
+ * touching a frame byte: one 32-byte record per arp_update / ndp_update the reference would call,
+ * in packet order.  Frames are read only; a byte at or past len reads as zero and never
+ * influences a result.  The batch holds FULL frames, as for upe_gpu_process_segmented: the NS / NA
+ * option walk reads up to len bytes of a frame.
+ *
+ * Marked packets: the rule upe_gpu_ingress_gather documents for d_ctrl (ctrl_table_write,
+ * csrc/upe_dev.h); info.ctrl counts them.
+ * ARP (src/worker.c:28-39): a marked ARP packet always yields a record — arp_update(ntohl(spa),
+ * sha).  The learn does not look at len: spa and sha bytes at or past len are zero.  The reply
+ * (src/worker.c:40-52), the port address and op play no part.
+ * NS / NA (src/worker.c:57-95): off = 78; while off + 2 <= len: ot = f[off], ol =
+ * (uint8_t)(f[off + 1] * 8) — the reference's uint8_t opt_len: a length byte of 32 wraps to 0, 33
+ * to 8; stop if ol == 0 or off + ol > len; a record — ndp_update(NS: the IPv6 source, NA: the
+ * target; mac = f[off + 2 .. off + 8)) — if (NS and ot == 1) or (NA and ot == 2); else off += ol.
+ * An NS / NA with no such option yields no record (it is still counted in ctrl).
+ * The records do not depend on any table: whether a table exists, or is full, is decided when
+ * they are applied (upe_neigh_apply_writes).
+ *
+ * d_writes[0 .. stored) are the records in ascending index, stored = min(writes, cap); nothing at
+ * or past d_writes + cap is written, and `writes` is the cap to retry with.  Asynchronous on
+ * `stream` (NULL: the context's), at most three launches; scratch lives in the context, so a
+ * context's calls are queued one after another.  Otherwise read-only with respect to the context:
+ * tables, counters, rule_stats, the L1 state, the latency histogram and upe_gpu_launch_info are
+ * untouched and no launch is counted.  n == 0 zeroes *d_info with first_write = UINT64_MAX and
+ * launches nothing.  -1 (upe_gpu_last_error()) before any launch: a NULL context; NULL d_frames or
+ * d_desc with n > 0; a NULL d_info; a NULL d_writes with cap > 0; d_writes not 16-byte aligned; n
+ * above 2^32 - 1 - UPE_CTRL_BLOCK.
+ * UPE_CTRL_BLOCK: packets per workgroup of the kernels (batch sizes around it are where tests
+ * look). */
+#define UPE_CTRL_BLOCK 1024
+enum { UPE_CW_ARP = 4, UPE_CW_NDP = 6 };
+typedef struct {        /* 32 bytes, every byte written */
+    uint32_t index;     /* packet position in the batch */
+    uint8_t kind;       /* UPE_CW_ARP: arp_update; UPE_CW_NDP: ndp_update */
+    uint8_t zero0;
+    uint16_t mac_off;   /* frame offset the MAC was read from: 22 (ARP sha), or the chosen
+                           option's offset + 2 (NDP) */
+    uint8_t mac[6];
+    uint16_t zero1;
+    uint8_t ip[16];     /* ARP: bytes 0-3 = ntohl(spa) as a little-endian word (upe_ip_addr_t.v4),
+                           bytes 4-15 zero.  NDP: the 16 wire bytes (NS: the IPv6 source, frame
+                           bytes 22..37; NA: the target, frame bytes 62..77) */
+} upe_ctrl_write_t;
+typedef struct {          /* device, 32 bytes */
+    uint64_t ctrl;        /* packets the marking rule selects (== ingress_gather's n_ctrl) */
+    uint64_t writes;      /* records the batch has */
+    uint64_t stored;      /* min(writes, cap): a prefix in packet order */
+    uint64_t first_write; /* index of the first record's packet, or UINT64_MAX */
+} upe_ctrl_info_t;
+
+int upe_gpu_ctrl_writes(upe_gpu_ctx_t *ctx, const uint8_t *d_frames, const uint64_t *d_desc,
+                        size_t n, upe_ctrl_write_t *d_writes, size_t cap,
+                        upe_ctrl_info_t *d_info, void *stream);
+
+/* upe_gpu_ctrl_writes' exact host twin (upe_host.c): the same bytes in writes[0 .. stored) and
+ * *info for a batch in host memory.  No GPU needed.  0 / -1 (upe_host_last_error()): NULL frames
+ * or desc with n > 0, a NULL info, NULL writes with cap > 0, n above 2^32 - 1 - UPE_CTRL_BLOCK. */
+int upe_ctrl_writes_host(const uint8_t *frames, const uint64_t *desc, size_t n,
+                         upe_ctrl_write_t *writes, size_t cap, upe_ctrl_info_t *info);
+
+/* The records applied, in order, to the caller's slot arrays: arp_update (src/arp_table.c:26-53:
+ * from slot ip & (capacity - 1), the first slot that is free or holds the address, at most
+ * capacity probes) and ndp_update (src/ndp_table.c:39-65, from hash_ipv6 :6-17), update_at = now
+ * on every slot written; a full table with no matching slot is left alone.  *applied (optional) =
+ * the records whose family has a table (capacity > 0): what upe_gpu_process_segmented counts in
+ * n_writes.  Capacities are powers of two, or NULL with capacity 0.  Everything is checked before
+ * the first write: -1 (upe_host_last_error()), with nothing changed, for a bad capacity, a missing
+ * table, NULL writes with count > 0, or a record whose kind is neither UPE_CW_ARP nor UPE_CW_NDP.
+ * The caller then uploads the tables (upe_gpu_load_neigh). */
+int upe_neigh_apply_writes(upe_arp_entry_t *arp, size_t arp_capacity,
+                           upe_ndp_entry_t *ndp, size_t ndp_capacity,
+                           const upe_ctrl_write_t *writes, size_t count, int64_t now,
+                           size_t *applied);
+
 /* Wait for all work queued on the context's stream (or `stream`). */
 int upe_gpu_sync(upe_gpu_ctx_t *ctx, void *stream);
 
@@ -1100,6 +1179,11 @@ UPE_STATIC_ASSERT(sizeof(upe_pktbuf_t) == 2064, "pktbuf_t layout");
 UPE_STATIC_ASSERT(offsetof(upe_pktbuf_t, len) == 8, "pktbuf_t.len");
 UPE_STATIC_ASSERT(offsetof(upe_pktbuf_t, data) == 16, "pktbuf_t.data");
 UPE_STATIC_ASSERT(sizeof(upe_ingress_info_t) == 64, "upe_ingress_info_t layout");
+UPE_STATIC_ASSERT(sizeof(upe_ctrl_write_t) == 32, "upe_ctrl_write_t layout");
+UPE_STATIC_ASSERT(offsetof(upe_ctrl_write_t, mac_off) == 6, "upe_ctrl_write_t.mac_off");
+UPE_STATIC_ASSERT(offsetof(upe_ctrl_write_t, mac) == 8, "upe_ctrl_write_t.mac");
+UPE_STATIC_ASSERT(offsetof(upe_ctrl_write_t, ip) == 16, "upe_ctrl_write_t.ip");
+UPE_STATIC_ASSERT(sizeof(upe_ctrl_info_t) == 32, "upe_ctrl_info_t layout");
 UPE_STATIC_ASSERT(sizeof(upe_latency_hist_t) == 96, "latency_histogram_t layout");
 UPE_STATIC_ASSERT(offsetof(upe_latency_hist_t, total_count) == 64, "latency_histogram_t.total_count");
 UPE_STATIC_ASSERT(offsetof(upe_latency_hist_t, min_ns) == 72, "latency_histogram_t.min_ns");

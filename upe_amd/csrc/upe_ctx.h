@@ -1,8 +1,8 @@
 // upe_ctx.h — the context (struct upe_gpu_ctx) and the few helpers every entry point of the
 // library uses, for the units that hold the host side of the extern "C" ABI: upe_gpu.hip (the
 // classify path, create / destroy, the loads), upe_rx.hip, upe_egress.hip, upe_ingress.hip,
-// upe_latency.hip, upe_hostpath.hip and upe_segment.hip.  Internal: not part of the ABI, and
-// nothing declared here is exported.
+// upe_latency.hip, upe_ctrl.hip, upe_hostpath.hip and upe_segment.hip.  Internal: not part of
+// the ABI, and nothing declared here is exported.
 #ifndef UPE_CTX_H
 #define UPE_CTX_H
 
@@ -322,6 +322,7 @@ struct upe_gpu_ctx {
     DevBuf<uint8_t> rx_scratch;           // upe_gpu_rx_dispatch: the passes' tile table (upe_rx.hip)
     DevBuf<uint8_t> eg_scratch;           // upe_gpu_egress_pack: the tile table (upe_egress.hip)
     DevBuf<uint8_t> in_scratch;           // upe_gpu_ingress_gather: tile table + meta (upe_ingress.hip)
+    DevBuf<uint8_t> cw_scratch;           // upe_gpu_ctrl_writes: tile table + words (upe_ctrl.hip)
     DevBuf<unsigned long long> ring_wg;   // ring launches: per-batch counters + time origin
     // the latency histogram (upe_gpu_latency_record, upe_latency.hip): replicas of the 12 words
     // of a upe_latency_hist_t, touched by nothing but the four latency calls

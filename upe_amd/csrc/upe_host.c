@@ -20,6 +20,10 @@
  *   upe_neigh_lookup_host  arp_get_mac / ndp_get_mac (src/arp_table.c:55-80,
  *                       src/ndp_table.c:67-86) per flow key over the slot arrays: the host
  *                       equivalent of upe_gpu_resolve_keys.
+ *   upe_ctrl_writes_host   the table writes of handle_control_packet (src/worker.c:23-104) for a
+ *                       batch, as records: the host equivalent of upe_gpu_ctrl_writes.
+ *   upe_neigh_apply_writes arp_update / ndp_update (src/arp_table.c:26-53,
+ *                       src/ndp_table.c:39-65) of those records on the slot arrays.
  */
 #define _GNU_SOURCE
 #include <arpa/inet.h>
@@ -488,6 +492,130 @@ int upe_neigh_lookup_host(const upe_arp_entry_t *arp, size_t arp_capacity,
                : keys[k].ip_ver == 6 ? ndp_probe(ndp, ndp_capacity, d)
                                      : 0;
     }
+    return 0;
+}
+
+/* ---- control writes --------------------------------------------------------------------- */
+
+/* frame byte j, zero at or past len (a zero-filled pktbuf) */
+static uint32_t byte_at(const uint8_t *f, uint32_t len, uint32_t j) { return j < len ? f[j] : 0u; }
+
+/* ctrl_table_write (csrc/upe_dev.h), the rule of upe_gpu_ingress_gather's d_ctrl */
+static int ctrl_marked(const uint8_t *f, uint32_t len) {
+    const uint32_t et = byte_at(f, len, 12) << 8 | byte_at(f, len, 13);
+    if (et == 0x0806u)
+        return byte_at(f, len, 14) == 0 && byte_at(f, len, 15) == 1 && byte_at(f, len, 16) == 8 &&
+               byte_at(f, len, 17) == 0 && byte_at(f, len, 18) == 6 && byte_at(f, len, 19) == 4;
+    return et == 0x86DDu && len >= 78 && byte_at(f, len, 20) == 58 &&
+           (byte_at(f, len, 54) == 135 || byte_at(f, len, 54) == 136);
+}
+
+/* One marked frame's record (src/worker.c:28-39 ARP, :57-95 NS / NA): 1 when it has one. */
+static int ctrl_record(const uint8_t *f, uint32_t len, uint32_t index, upe_ctrl_write_t *w) {
+    memset(w, 0, sizeof *w);
+    w->index = index;
+    if (byte_at(f, len, 12) == 0x08) {
+        w->kind = UPE_CW_ARP;
+        w->mac_off = 22;
+        for (uint32_t j = 0; j < 6; j++) w->mac[j] = (uint8_t)byte_at(f, len, 22 + j);
+        /* ntohl(spa) as upe_ip_addr_t.v4 holds it on a little-endian host */
+        for (uint32_t j = 0; j < 4; j++) w->ip[j] = (uint8_t)byte_at(f, len, 31 - j);
+        return 1;
+    }
+    const int na = f[54] == 136; /* len >= 78 */
+    for (uint32_t off = 78; off + 2 <= len;) {
+        const uint8_t ot = f[off];
+        const uint8_t ol = (uint8_t)(f[off + 1] * 8u); /* src/worker.c:73: 32 wraps to 0 */
+        if (ol == 0 || off + ol > len) break;
+        if (ot == (na ? 2 : 1)) {
+            w->kind = UPE_CW_NDP;
+            w->mac_off = (uint16_t)(off + 2);
+            memcpy(w->mac, f + off + 2, 6);
+            memcpy(w->ip, f + (na ? 62 : 22), 16);
+            return 1;
+        }
+        off += ol;
+    }
+    return 0;
+}
+
+int upe_ctrl_writes_host(const uint8_t *frames, const uint64_t *desc, size_t n,
+                         upe_ctrl_write_t *writes, size_t cap, upe_ctrl_info_t *info) {
+    if (!info || (n && (!frames || !desc)) || (cap && !writes))
+        return host_fail("upe_ctrl_writes_host: null argument%.0d%s", 0, "");
+    if (n > 0xFFFFFFFFull - UPE_CTRL_BLOCK)
+        return host_fail("upe_ctrl_writes_host: n must fit in 32 bits%.0d%s", 0, "");
+    memset(info, 0, sizeof *info);
+    info->first_write = UINT64_MAX;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t len = (uint32_t)(desc[i] & 0xFFFFu);
+        const uint8_t *f = frames + (desc[i] >> 16);
+        if (!ctrl_marked(f, len)) continue;
+        info->ctrl++;
+        upe_ctrl_write_t w;
+        if (!ctrl_record(f, len, (uint32_t)i, &w)) continue;
+        if (info->writes == 0) info->first_write = i;
+        if (info->writes < cap) writes[info->stored++] = w;
+        info->writes++;
+    }
+    return 0;
+}
+
+/* arp_update, src/arp_table.c:26-53: the slot to write, or NULL when the table is full of other
+ * addresses. */
+static upe_arp_entry_t *arp_slot(upe_arp_entry_t *t, size_t cap, uint32_t ip) {
+    for (size_t k = 0, s = ip & (cap - 1); k < cap; k++, s = (s + 1) & (cap - 1))
+        if (!t[s].valid || t[s].ip == ip) return &t[s];
+    return NULL;
+}
+
+/* ndp_update, src/ndp_table.c:39-65 */
+static upe_ndp_entry_t *ndp_slot(upe_ndp_entry_t *t, size_t cap, const uint8_t ip[16]) {
+    const size_t home = ld_le32(ip) ^ ld_le32(ip + 4) ^ ld_le32(ip + 8) ^ ld_le32(ip + 12);
+    for (size_t k = 0, s = home & (cap - 1); k < cap; k++, s = (s + 1) & (cap - 1))
+        if (!t[s].valid || memcmp(t[s].ip, ip, 16) == 0) return &t[s];
+    return NULL;
+}
+
+int upe_neigh_apply_writes(upe_arp_entry_t *arp, size_t arp_capacity, upe_ndp_entry_t *ndp,
+                           size_t ndp_capacity, const upe_ctrl_write_t *writes, size_t count,
+                           int64_t now, size_t *applied) {
+    if ((arp_capacity & (arp_capacity - 1)) != 0 || (ndp_capacity & (ndp_capacity - 1)) != 0)
+        return host_fail("upe_neigh_apply_writes: capacity must be a power of two%.0d%s", 0, "");
+    if ((arp_capacity && !arp) || (ndp_capacity && !ndp) || (count && !writes))
+        return host_fail("upe_neigh_apply_writes: null argument%.0d%s", 0, "");
+    for (size_t k = 0; k < count; k++)
+        if (writes[k].kind != UPE_CW_ARP && writes[k].kind != UPE_CW_NDP)
+            return host_fail("upe_neigh_apply_writes: record %d has an unknown kind%s", (int)k, "");
+    size_t done = 0;
+    for (size_t k = 0; k < count; k++) {
+        const upe_ctrl_write_t *w = &writes[k];
+        if (w->kind == UPE_CW_ARP) {
+            if (!arp_capacity) continue;
+            done++;
+            const uint32_t ip = ld_le32(w->ip);
+            upe_arp_entry_t *e = arp_slot(arp, arp_capacity, ip);
+            if (!e) continue;
+            if (!e->valid) {
+                e->valid = true;
+                e->ip = ip;
+            }
+            memcpy(e->mac, w->mac, 6);
+            e->update_at = now;
+        } else {
+            if (!ndp_capacity) continue;
+            done++;
+            upe_ndp_entry_t *e = ndp_slot(ndp, ndp_capacity, w->ip);
+            if (!e) continue;
+            if (!e->valid) {
+                e->valid = true;
+                memcpy(e->ip, w->ip, 16);
+            }
+            memcpy(e->mac, w->mac, 6);
+            e->update_at = now;
+        }
+    }
+    if (applied) *applied = done;
     return 0;
 }
 

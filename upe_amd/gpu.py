@@ -16,7 +16,8 @@ import os
 
 import numpy as np
 
-from .layout import (ARP_DTYPE, BATCH_INFO_DTYPE, COUNTERS_DTYPE, FLOW_KEY_DTYPE, L1_DTYPE,
+from .layout import (ARP_DTYPE, BATCH_INFO_DTYPE, COUNTERS_DTYPE, CTRL_INFO_DTYPE,
+                     CTRL_WRITE_DTYPE, FLOW_KEY_DTYPE, L1_DTYPE,
                      EGRESS_INFO_DTYPE, INGRESS_INFO_DTYPE, LAUNCH_INFO_DTYPE, NDP_DTYPE, RULE_DTYPE, RULE_INDEX_INFO_DTYPE,
                      RULE_STAT_DTYPE)
 
@@ -48,6 +49,7 @@ INGRESS_REF, INGRESS_WINDOW, INGRESS_FULL = 0, 1, 2   # UPE_INGRESS_REF / _WINDO
 
 # upe_gpu_latency_record (include/upe_gpu.h)
 LATENCY_BLOCK = 1024      # UPE_LATENCY_BLOCK: packets per workgroup pass of the histogram kernel
+CTRL_BLOCK = 1024         # UPE_CTRL_BLOCK: packets per workgroup of the control-write kernels
 
 
 # upe_tx_batch_fn: int (*)(void *user, const uint8_t *const *frames, const size_t *lens, int count)
@@ -151,6 +153,7 @@ def _load() -> ctypes.CDLL:
         "upe_neigh_image_free": (None, [P]),
         "upe_gpu_load_neigh_image": (I, [P, P]),
         "upe_gpu_resolve_keys": (I, [P, P, P, SZ, P, P]),
+        "upe_gpu_ctrl_writes": (I, [P, P, P, SZ, P, SZ, P, P]),
         "upe_gpu_process_segmented": (I, [P, P, P, P, SZ, P, SZ, P, SZ, ctypes.c_int64, P, P]),
         "upe_gpu_process_emit": (I, [P, P, P, P, P, SZ, P]),
         "upe_gpu_process_emit_tx": (I, [P, P, P, P, P, P, P, SZ, P]),
@@ -177,6 +180,8 @@ def _load() -> ctypes.CDLL:
         "upe_rules_load_ini": (I, [ctypes.c_char_p, P, SZ, P]),
         "upe_rules_match_host": (I, [P, SZ, P, SZ, P, P]),
         "upe_neigh_lookup_host": (I, [P, SZ, P, SZ, P, SZ, P]),
+        "upe_ctrl_writes_host": (I, [P, P, SZ, P, SZ, P]),
+        "upe_neigh_apply_writes": (I, [P, SZ, P, SZ, P, SZ, ctypes.c_int64, P]),
         "upe_pcap_read": (I, [ctypes.c_char_p, P, SZ, P, SZ, P]),
         "upe_host_last_error": (ctypes.c_char_p, []),
         "upe_latency_init": (None, [P]),
@@ -225,7 +230,8 @@ EXPORTED = ("upe_gpu_last_error", "upe_gpu_device_count", "upe_gpu_local_cpus", 
             "upe_gpu_latency_record", "upe_gpu_get_latency", "upe_gpu_reset_latency",
             "upe_gpu_parse_keys", "upe_gpu_match_keys",
             "upe_neigh_compile", "upe_neigh_image_free", "upe_gpu_load_neigh_image",
-            "upe_gpu_resolve_keys", "upe_neigh_lookup_host")
+            "upe_gpu_resolve_keys", "upe_neigh_lookup_host",
+            "upe_gpu_ctrl_writes", "upe_ctrl_writes_host", "upe_neigh_apply_writes")
 
 
 def _check(rc: int, what: str) -> None:
@@ -587,6 +593,29 @@ class GpuWorker:
                                         _dev_ptr(keys) or None, n, _dev_ptr(mac) or None,
                                         stream or None), "upe_gpu_resolve_keys")
 
+    # ---- control writes ----
+    def ctrl_writes(self, frames, desc, n: int, writes, cap: int, info, stream=None) -> None:
+        """upe_gpu_ctrl_writes: the neighbour-table writes of a resident batch's control packets
+        as records in packet order (ctrl.ctrl_writes is the same on the host).  Device buffers:
+        writes (cap CTRL_WRITE_DTYPE records, 32 bytes each, 16-byte aligned; None with cap 0),
+        info (32 bytes, CTRL_INFO_DTYPE)."""
+        _check(LIB.upe_gpu_ctrl_writes(self._ctx, _dev_ptr(frames) or None, _dev_ptr(desc) or None,
+                                       n, _dev_ptr(writes) or None, cap, _dev_ptr(info) or None,
+                                       stream or None), "upe_gpu_ctrl_writes")
+
+    def fetch_ctrl_writes(self, writes, info, stream=None):
+        """(the `stored` records, the upe_ctrl_info_t) a ctrl_writes call left on the device
+        (synchronises)."""
+        x = np.zeros(1, CTRL_INFO_DTYPE)
+        self.sync(stream)
+        self.d2h(x, info)
+        self.sync()
+        out = np.zeros(int(x["stored"][0]), CTRL_WRITE_DTYPE)
+        if len(out):
+            self.d2h(out.view(np.uint8).reshape(-1), writes)
+            self.sync()
+        return out, x[0]
+
     def sync(self, stream=None) -> None:
         _check(LIB.upe_gpu_sync(self._ctx, stream or None), "upe_gpu_sync")
 
@@ -723,6 +752,44 @@ def neigh_lookup_host(arp, ndp, keys: np.ndarray) -> np.ndarray:
                                  _np_ptr(out) if len(k) else None) != 0:
         raise UpeGpuError(f"upe_neigh_lookup_host: {LIB.upe_host_last_error().decode()}")
     return out
+
+
+def ctrl_writes_host(frames: np.ndarray, desc: np.ndarray, cap: int | None = None):
+    """upe_ctrl_writes_host: (the stored records, the CTRL_INFO_DTYPE record) of a host batch;
+    cap None: room for every record (a first call with cap 0 sizes it)."""
+    f = np.ascontiguousarray(frames, np.uint8)
+    d = np.ascontiguousarray(desc, np.uint64)
+    info = np.zeros(1, CTRL_INFO_DTYPE)
+
+    def call(out, room):
+        if LIB.upe_ctrl_writes_host(_np_ptr(f) if f.size else None, _np_ptr(d) if d.size else None,
+                                    len(d), _np_ptr(out) if room else None, room,
+                                    _np_ptr(info)) != 0:
+            raise UpeGpuError(f"upe_ctrl_writes_host: {LIB.upe_host_last_error().decode()}")
+
+    if cap is None:
+        call(None, 0)
+        cap = int(info["writes"][0])
+    out = np.zeros(max(cap, 1), CTRL_WRITE_DTYPE)
+    call(out, cap)
+    return out[:int(info["stored"][0])].copy(), info[0]
+
+
+def neigh_apply_writes(arp, ndp, writes: np.ndarray, now: int) -> int:
+    """upe_neigh_apply_writes: arp_update / ndp_update of each record on the slot arrays (in
+    place; None or empty: no table of that family); returns `applied`."""
+    a = np.zeros(0, ARP_DTYPE) if arp is None else arp
+    b = np.zeros(0, NDP_DTYPE) if ndp is None else ndp
+    assert a.dtype == ARP_DTYPE and b.dtype == NDP_DTYPE
+    assert a.flags.c_contiguous and b.flags.c_contiguous
+    w = np.ascontiguousarray(writes, CTRL_WRITE_DTYPE)
+    applied = ctypes.c_size_t(0)
+    if LIB.upe_neigh_apply_writes(_np_ptr(a) if len(a) else None, len(a),
+                                  _np_ptr(b) if len(b) else None, len(b),
+                                  _np_ptr(w) if len(w) else None, len(w), int(now),
+                                  ctypes.byref(applied)) != 0:
+        raise UpeGpuError(f"upe_neigh_apply_writes: {LIB.upe_host_last_error().decode()}")
+    return applied.value
 
 
 def pcap_read(path: str):

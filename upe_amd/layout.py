@@ -67,6 +67,13 @@ EGRESS_INFO_DTYPE = np.dtype([("frames", "<u8"), ("packed", "<u8"), ("bytes", "<
 INGRESS_INFO_DTYPE = np.dtype([("packets", "<u8"), ("packed", "<u8"), ("bytes", "<u8"),
                                ("need", "<u8"), ("bad", "<u8"), ("first_bad", "<u8"),
                                ("n_ctrl", "<u8"), ("first_ctrl", "<u8")])
+# upe_ctrl_write_t / upe_ctrl_info_t (include/upe_gpu.h)
+CTRL_WRITE_DTYPE = np.dtype({"names": ["index", "kind", "zero0", "mac_off", "mac", "zero1", "ip"],
+                             "formats": ["<u4", "u1", "u1", "<u2", ("u1", 6), "<u2", ("u1", 16)],
+                             "offsets": [0, 4, 5, 6, 8, 14, 16], "itemsize": 32})
+CTRL_INFO_DTYPE = np.dtype([("ctrl", "<u8"), ("writes", "<u8"), ("stored", "<u8"),
+                            ("first_write", "<u8")])
+CW_ARP, CW_NDP = 4, 6        # UPE_CW_ARP / UPE_CW_NDP
 # pktbuf_t (reference include/pktbuf.h:8-14; upe_pktbuf_t, 2064 bytes)
 PKTBUF_DATA = 2048
 PKTBUF_DTYPE = np.dtype([("timestamp", "<u8"), ("len", "<u8"), ("data", "u1", (PKTBUF_DATA,))])
