@@ -16,7 +16,7 @@ from upe_amd import rx
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = ("config_a", "config_b_small", "config_c_small", "config_cf_small", "config_d_small",
          "edge_zero", "ndp_walk")
-RINGS = (1, 2, 4, 64)
+RINGS = (1, 2, 4, 8, 16, 32, 64)
 # fallback packets per case (parse_flow_key fails): the round-robin path is exercised
 FALLBACKS = {"config_c_small": 354, "config_d_small": 295, "edge_zero": 328, "ndp_walk": 24}
 
