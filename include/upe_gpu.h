@@ -983,6 +983,82 @@ int upe_neigh_apply_writes(upe_arp_entry_t *arp, size_t arp_capacity,
                            const upe_ctrl_write_t *writes, size_t count, int64_t now,
                            size_t *applied);
 
+/* The records applied to the LOADED snapshot, on the device, where that moves nothing
+ * (csrc/upe_neigh_patch.hip): a refresh — a record whose address the snapshot already holds —
+ * rewrites the MAC of the one index slot a lookup of that address answers from, as arp_update /
+ * ndp_update rewrite the slot their probe, which is the lookup's, arrives at (src/arp_table.c:26-80,
+ * src/ndp_table.c:39-86).  No index is rebuilt and nothing is uploaded.
+ * Address held: a UPE_CW_ARP record's when arp_get_mac of ip bytes 0-3 (the little-endian word)
+ * hits in the loaded snapshot, a UPE_CW_NDP record's when ndp_get_mac of the 16 bytes does — the
+ * answers upe_gpu_resolve_keys gives before the call.
+ * Result: the snapshot after the call is the snapshot before it with the held records applied in
+ * rank order (rank: position in d_writes): of the held records aimed at one slot the one of
+ * highest rank supplies the six MAC bytes; the slot's address, its used bit and every slot no
+ * record aims at keep every bit.
+ * Missed records: a record whose address is not held — a new neighbour, a family whose index is
+ * empty, a kind that is neither UPE_CW_ARP nor UPE_CW_NDP — changes nothing.  d_miss[0 .. missed)
+ * (optional) are their ranks, ascending; nothing at or past d_miss + missed is written; patched +
+ * missed == records.  The caller applies them on the host, in order (upe_neigh_apply_writes, then
+ * upe_gpu_load_neigh); applying every held record here and the missed ones there gives the
+ * reference's tables (DESIGN.md §3 has the argument).
+ * Derived state: what a snapshot load does to the context after its swap happens after a patch
+ * too, on `stream`: whether the L1 entries still agree with the tables is asked again.  The L1
+ * entries themselves are not touched (the reference never invalidates last_arp_ip / last_ndp_ip: a
+ * packet aimed at an L1 entry keeps getting the old MAC).
+ * Asynchronous on `stream` (NULL: the context's) and ordered like a launch: a classify queued
+ * before the call reads the old MACs, one queued after it the new ones.  Three launches of its
+ * own, then the one or two of the derived state; scratch lives in the context.  Counters,
+ * rule_stats, the latency histogram, upe_gpu_launch_info and any upe_neigh_image_t the caller
+ * holds are untouched (an image is a value: the context's device copy alone changes), and no
+ * launch is counted.  count == 0 zeroes *d_info with first_miss = UINT64_MAX and launches
+ * nothing.  -1 (upe_gpu_last_error()) before any launch: a NULL context; a NULL d_info; a NULL
+ * d_writes with count > 0; d_writes not 16-byte aligned; count above 2^32 - 1 - UPE_PATCH_BLOCK.
+ * UPE_PATCH_BLOCK: records per workgroup of the kernels (counts around it are where tests look). */
+#define UPE_PATCH_BLOCK 256
+typedef struct {          /* device, 32 bytes, every byte written */
+    uint64_t records;     /* count */
+    uint64_t patched;     /* records whose address the loaded snapshot holds */
+    uint64_t missed;      /* the rest */
+    uint64_t first_miss;  /* rank of the first missed record, or UINT64_MAX */
+} upe_neigh_patch_info_t;
+
+int upe_gpu_neigh_patch(upe_gpu_ctx_t *ctx, const upe_ctrl_write_t *d_writes, size_t count,
+                        uint32_t *d_miss /* count entries, optional */,
+                        upe_neigh_patch_info_t *d_info, void *stream);
+
+/* upe_gpu_neigh_patch's exact host twin (csrc/upe_rules.cpp) on a compiled snapshot
+ * (upe_neigh_compile): the same change to the image, the same bytes in miss[0 .. missed) and
+ * *info.  No GPU needed.  0 / -1 (upe_gpu_last_error()): a NULL image or info, NULL writes with
+ * count > 0, count above 2^32 - 1 - UPE_PATCH_BLOCK.
+ * upe_neigh_image_lookup_host: what a context that has loaded the image answers
+ * (upe_gpu_resolve_keys' format and rules), by the index's own three-slot lookup. */
+int upe_neigh_patch_host(upe_neigh_image_t *image, const upe_ctrl_write_t *writes, size_t count,
+                         uint32_t *miss /* count entries, optional */,
+                         upe_neigh_patch_info_t *info);
+int upe_neigh_image_lookup_host(const upe_neigh_image_t *image, const upe_flow_key_t *keys,
+                                size_t n, uint64_t *mac);
+
+/* upe_gpu_process_segmented without a frame byte on the host (csrc/upe_segment.hip): the same
+ * batch, arguments and outputs, bit for bit — verdict words, frames, counters, rule_stats, the L1
+ * state and the caller's slot arrays (update_at included).  The batch's records come from
+ * upe_gpu_ctrl_writes (one copy of its info and records to the host, one synchronisation); the
+ * batch is cut after every marked packet, as there (when some marked packet has no record, their
+ * positions are listed on the device first, one more small copy); for each record, in order, the
+ * segment up to and including its packet is queued, the record is
+ * applied to the host arrays (upe_neigh_apply_writes), and the device follows: a record whose
+ * address the arrays held (upe_neigh_lookup_host, before the write) is queued as a
+ * upe_gpu_neigh_patch of that one record — no synchronisation, no rebuild — and any other takes
+ * upe_gpu_load_neigh.  A record whose family has no table (capacity 0) is skipped, as there.
+ * Synchronous at return.  A batch without records costs the upe_gpu_ctrl_writes pass and one
+ * classify.  info (optional): writes = upe_gpu_process_segmented's *n_writes; patched + rebuilds
+ * == writes; ctrl = the marked packets. */
+typedef struct { uint64_t writes, patched, rebuilds, ctrl; } upe_segment_info_t;   /* host */
+int upe_gpu_process_segmented_resident(upe_gpu_ctx_t *ctx, uint8_t *d_frames,
+                                       const uint64_t *d_desc, uint32_t *d_verdict, size_t n,
+                                       upe_arp_entry_t *arp, size_t arp_capacity,
+                                       upe_ndp_entry_t *ndp, size_t ndp_capacity, int64_t now,
+                                       upe_segment_info_t *info, void *stream);
+
 /* Wait for all work queued on the context's stream (or `stream`). */
 int upe_gpu_sync(upe_gpu_ctx_t *ctx, void *stream);
 

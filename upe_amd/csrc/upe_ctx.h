@@ -1,7 +1,7 @@
 // upe_ctx.h — the context (struct upe_gpu_ctx) and the few helpers every entry point of the
 // library uses, for the units that hold the host side of the extern "C" ABI: upe_gpu.hip (the
 // classify path, create / destroy, the loads), upe_rx.hip, upe_egress.hip, upe_ingress.hip,
-// upe_latency.hip, upe_ctrl.hip, upe_hostpath.hip and upe_segment.hip.  Internal: not part of
+// upe_latency.hip, upe_ctrl.hip, upe_neigh_patch.hip, upe_hostpath.hip and upe_segment.hip.  Internal: not part of
 // the ABI, and nothing declared here is exported.
 #ifndef UPE_CTX_H
 #define UPE_CTX_H
@@ -316,6 +316,9 @@ struct upe_gpu_ctx {
         DevBuf<uint64_t> count;
         DevBuf<uint8_t> win;
         DevBuf<uint32_t> lens;
+        // upe_gpu_process_segmented_resident: the batch's records behind their upe_ctrl_info_t
+        DevBuf<uint4> rec;
+        DevBuf<upe_neigh_patch_info_t> pinfo;   // its patches' info (nobody reads it)
     } seg;
     // single-use scratch
     DevBuf<uint32_t> compact_counts;      // upe_gpu_compact: per-block counts
@@ -323,6 +326,8 @@ struct upe_gpu_ctx {
     DevBuf<uint8_t> eg_scratch;           // upe_gpu_egress_pack: the tile table (upe_egress.hip)
     DevBuf<uint8_t> in_scratch;           // upe_gpu_ingress_gather: tile table + meta (upe_ingress.hip)
     DevBuf<uint8_t> cw_scratch;           // upe_gpu_ctrl_writes: tile table + words (upe_ctrl.hip)
+    DevBuf<uint8_t> np_scratch;           // upe_gpu_neigh_patch: tile table + words (upe_neigh_patch.hip)
+    DevBuf<uint32_t> np_owner;            // its owner word per index slot, ARP then NDP: zero between calls
     DevBuf<unsigned long long> ring_wg;   // ring launches: per-batch counters + time origin
     // the latency histogram (upe_gpu_latency_record, upe_latency.hip): replicas of the 12 words
     // of a upe_latency_hist_t, touched by nothing but the four latency calls
@@ -400,6 +405,14 @@ struct ProcessReq {
 // One batch through the classify launch (upe_gpu.hip); the host paths (upe_hostpath.hip) call it
 // with requests of their own.
 UPE_INTERNAL int process_impl(upe_gpu_ctx_t* c, const ProcessReq& q);
+
+// Around a change of the loaded neighbour snapshot's MACs in place (upe_gpu_neigh_patch,
+// upe_neigh_patch.hip), both queued on `s` (upe_gpu.hip, beside the load they mirror).
+// neigh_patching: `s` ordered after everything the context has queued, and the last batch's L1
+// outcome folded into the state the next batch starts from, before the tables change.
+// neigh_patched: do the L1 entries agree with the tables now?  (The entries themselves stay.)
+UPE_INTERNAL int neigh_patching(upe_gpu_ctx_t* c, hipStream_t s);
+UPE_INTERNAL int neigh_patched(upe_gpu_ctx_t* c, hipStream_t s);
 
 // The empty latency histogram's device image (upe_latency.hip): every replica in the
 // upe_latency_init state.  Context creation uploads it.

@@ -1778,23 +1778,26 @@ DevL1* l1_slot(upe_gpu_ctx* c, uint64_t k) { return &c->st->l1[k % 2].s; }
 BatchAcc* acc_slot(upe_gpu_ctx* c, uint64_t k) { return &c->st->acc[k % 3]; }
 TilePay* pay_slot(upe_gpu_ctx* c, uint64_t k) { return c->pay + (size_t)(k % 2) * c->paycap; }
 
-// Does the L1 state the next batch starts from agree with the tables?  (After l1_sync.)
-int refresh(upe_gpu_ctx* c) {
-    if (order_on(c, c->stream) != 0) return -1;
+// Does the L1 state the next batch starts from agree with the tables?  (After l1_sync.)  On the
+// context's stream, or on `s` (upe::neigh_patched).
+int refresh(upe_gpu_ctx* c, hipStream_t s = nullptr) {
+    if (!s) s = c->stream;
+    if (order_on(c, s) != 0) return -1;
     c->lb.no_lb = false;   // the entries may disagree with the new tables until a launch says not
     c->lb.reset_k = c->k;
-    hipLaunchKernelGGL(upe_refresh, dim3(1), dim3(64), 0, c->stream, l1_slot(c, c->k),
-                       arp_index(c), ndp_index(c));
+    hipLaunchKernelGGL(upe_refresh, dim3(1), dim3(64), 0, s, l1_slot(c, c->k), arp_index(c),
+                       ndp_index(c));
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
 // Fold the last batch's L1 outcome into l1[k % 2], the state the next batch starts from (and
 // clear it from that batch's accumulators, so the next launch does not fold it again).
-int l1_sync(upe_gpu_ctx* c) {
+int l1_sync(upe_gpu_ctx* c, hipStream_t s = nullptr) {
     if (c->k == 0) return 0;
-    if (order_on(c, c->stream) != 0) return -1;
-    hipLaunchKernelGGL(upe_l1_sync, dim3(1), dim3(64), 0, c->stream, l1_slot(c, c->k),
+    if (!s) s = c->stream;
+    if (order_on(c, s) != 0) return -1;
+    hipLaunchKernelGGL(upe_l1_sync, dim3(1), dim3(64), 0, s, l1_slot(c, c->k),
                        acc_slot(c, c->k + 2), pay_slot(c, c->k + 1));
     HIP_TRY(hipGetLastError());
     return 0;
@@ -2337,6 +2340,20 @@ int upe_gpu_load_neigh_image(upe_gpu_ctx_t* c, const upe_neigh_image_t* image) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
+
+}  // extern "C"
+
+// (upe_ctx.h) The two halves of what a load does around its swap, for a snapshot whose MACs change
+// in place (upe_gpu_neigh_patch, upe_neigh_patch.hip), queued on the patch's stream: before, the
+// last batch's L1 outcome into the starting state, after everything the context has queued;
+// after, the L1 entries' agreement with the changed tables.
+int upe::neigh_patching(upe_gpu_ctx_t* c, hipStream_t s) {
+    if (order_on(c, s) != 0) return -1;
+    return c->st ? l1_sync(c, s) : 0;
+}
+int upe::neigh_patched(upe_gpu_ctx_t* c, hipStream_t s) { return c->st ? refresh(c, s) : 0; }
+
+extern "C" {
 
 int upe_gpu_set_port(upe_gpu_ctx_t* c, const uint8_t eth_addr[6], uint32_t ip4_addr) {
     if (!c || !eth_addr) return fail("null argument");

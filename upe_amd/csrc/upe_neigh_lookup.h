@@ -79,6 +79,27 @@ __device__ __forceinline__ bool ndp_lookup(const NeighIndex& x, const uint32_t i
     return ndp_lookup_lds(x.t, x.bits, x.seed, ip, lo, hi);
 }
 
+// Where a lookup's answer lies: the slot (of the index's 2^bits) that arp_lookup / ndp_lookup
+// answer from, the first of the address's three candidates that hits, or kNone where they miss
+// (upe_neigh_patch.hip rewrites that slot's MAC; the lookups themselves decide "held" there).
+__device__ __forceinline__ uint32_t arp_slot_of(const NeighIndex& x, uint32_t ip) {
+    if (x.bits == 0) return kNone;
+    const uint32_t t1 = slot1(ip, x.seed, x.bits), t2 = slot2(ip, x.seed, x.bits),
+                   t3 = slot3(ip, x.seed, x.bits);
+    return arp_slot_hit(x.t[t1], ip) ? t1 : arp_slot_hit(x.t[t2], ip) ? t2
+         : arp_slot_hit(x.t[t3], ip) ? t3 : kNone;
+}
+__device__ __forceinline__ uint32_t ndp_slot_of(const NeighIndex& x, const uint32_t ip[4]) {
+    if (x.bits == 0) return kNone;
+    const uint32_t k = fold_v6(ip);
+    const uint32_t t1 = slot1(k, x.seed, x.bits), t2 = slot2(k, x.seed, x.bits),
+                   t3 = slot3(k, x.seed, x.bits);
+    return ndp_slot_hit(x.t[2 * t1], x.t[2 * t1 + 1], ip)   ? t1
+           : ndp_slot_hit(x.t[2 * t2], x.t[2 * t2 + 1], ip) ? t2
+           : ndp_slot_hit(x.t[2 * t3], x.t[2 * t3 + 1], ip) ? t3
+                                                            : kNone;
+}
+
 // Both families in one lookup: the IPv4 (ARP) and IPv6 (NDP) lanes of a wave issue their slot
 // loads together, so a mixed wave waits for one memory round trip, not one per family.
 __device__ __forceinline__ bool neigh_lookup(const NeighIndex& arp, const NeighIndex& ndp,

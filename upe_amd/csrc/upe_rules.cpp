@@ -1079,6 +1079,99 @@ extern "C" UPE_EXPORT upe_neigh_image_t* upe_neigh_compile(const upe_arp_entry_t
 
 extern "C" UPE_EXPORT void upe_neigh_image_free(upe_neigh_image_t* im) { delete im; }
 
+namespace {
+// The device lookups (arp_lookup / ndp_lookup with arp_slot_of / ndp_slot_of, upe_neigh_lookup.h)
+// on the host: the slot of the image's index that answers for an address — the first of its three
+// candidates that is used and holds it — or kNone.
+uint32_t arp_slot_host(const NeighImage& im, uint32_t ip) {
+    if (im.arp_bits == 0) return kNone;
+    const uint32_t c[3] = {slot1(ip, im.arp_seed, im.arp_bits), slot2(ip, im.arp_seed, im.arp_bits),
+                           slot3(ip, im.arp_seed, im.arp_bits)};
+    for (uint32_t t : c)
+        if (((im.arp[t].z >> 16) & 1u) && im.arp[t].x == ip) return t;
+    return kNone;
+}
+uint32_t ndp_slot_host(const NeighImage& im, const uint32_t ip[4]) {
+    if (im.ndp_bits == 0) return kNone;
+    const uint32_t k = fold_v6(ip);
+    const uint32_t c[3] = {slot1(k, im.ndp_seed, im.ndp_bits), slot2(k, im.ndp_seed, im.ndp_bits),
+                           slot3(k, im.ndp_seed, im.ndp_bits)};
+    for (uint32_t t : c) {
+        const uint4 &a = im.ndp[2 * (size_t)t], &m = im.ndp[2 * (size_t)t + 1];
+        if (((m.y >> 16) & 1u) && a.x == ip[0] && a.y == ip[1] && a.z == ip[2] && a.w == ip[3])
+            return t;
+    }
+    return kNone;
+}
+// A slot's MAC words in upe_gpu_resolve_keys' format.
+uint64_t found(uint32_t lo, uint32_t hi) {
+    return (uint64_t)lo | (uint64_t)((hi & 0xFFFFu) | 1u << 16) << 32;
+}
+}  // namespace
+
+// upe_gpu_resolve_keys over an image on the host (include/upe_gpu.h).
+extern "C" UPE_EXPORT int upe_neigh_image_lookup_host(const upe_neigh_image_t* image,
+                                                      const upe_flow_key_t* keys, size_t n,
+                                                      uint64_t* mac) {
+    if (!image || (n && (!keys || !mac))) return fail("null argument");
+    const NeighImage& im = image->im;
+    for (size_t i = 0; i < n; ++i) {
+        const uint8_t* d = keys[i].dst_ip.v6;
+        mac[i] = 0;
+        if (keys[i].ip_ver == 4) {
+            const uint32_t t = arp_slot_host(im, le32(d));
+            if (t != kNone) mac[i] = found(im.arp[t].y, im.arp[t].z);
+        } else if (keys[i].ip_ver == 6) {
+            const uint32_t ip[4] = {le32(d), le32(d + 4), le32(d + 8), le32(d + 12)};
+            const uint32_t t = ndp_slot_host(im, ip);
+            if (t != kNone) mac[i] = found(im.ndp[2 * (size_t)t + 1].x, im.ndp[2 * (size_t)t + 1].y);
+        }
+    }
+    return 0;
+}
+
+// upe_gpu_neigh_patch's twin (include/upe_gpu.h; the kernels: upe_neigh_patch.hip).  "Held" is
+// held before the call: a record rewrites MAC bytes only, which no lookup's hit depends on, so the
+// records go in rank order, one after another, and the last one aimed at a slot stays.
+extern "C" UPE_EXPORT int upe_neigh_patch_host(upe_neigh_image_t* image,
+                                               const upe_ctrl_write_t* writes, size_t count,
+                                               uint32_t* miss, upe_neigh_patch_info_t* info) {
+    if (!image || !info || (count && !writes)) return fail("null argument");
+    if (count > 0xFFFFFFFFull - UPE_PATCH_BLOCK) return fail("count must fit in 32 bits");
+    NeighImage& im = image->im;
+    uint64_t missed = 0, first = ~0ull;
+    for (size_t i = 0; i < count; ++i) {
+        const upe_ctrl_write_t& w = writes[i];
+        const uint32_t lo = mac_lo(w.mac), hi = mac_hi(w.mac);
+        uint32_t t = kNone;
+        if (w.kind == UPE_CW_ARP) {
+            t = arp_slot_host(im, le32(w.ip));
+            if (t != kNone) {
+                im.arp[t].y = lo;
+                im.arp[t].z = (im.arp[t].z & 0xFFFF0000u) | hi;
+            }
+        } else if (w.kind == UPE_CW_NDP) {
+            const uint32_t ip[4] = {le32(w.ip), le32(w.ip + 4), le32(w.ip + 8), le32(w.ip + 12)};
+            t = ndp_slot_host(im, ip);
+            if (t != kNone) {
+                uint4& m = im.ndp[2 * (size_t)t + 1];
+                m.x = lo;
+                m.y = (m.y & 0xFFFF0000u) | hi;
+            }
+        }
+        if (t == kNone) {
+            if (missed == 0) first = i;
+            if (miss) miss[missed] = (uint32_t)i;
+            ++missed;
+        }
+    }
+    info->records = count;
+    info->patched = count - missed;
+    info->missed = missed;
+    info->first_miss = first;
+    return 0;
+}
+
 // (diagnostic, not part of the ABI) the same, and per key and tree of its family (first 16):
 // levels walked (prof_depth[16 * i + t]) and leaf entries read (prof_steps[16 * i + t])
 extern "C" int upe_tree_profile_host(const upe_rule_t* rules, size_t count,

@@ -17,7 +17,8 @@ import os
 import numpy as np
 
 from .layout import (ARP_DTYPE, BATCH_INFO_DTYPE, COUNTERS_DTYPE, CTRL_INFO_DTYPE,
-                     CTRL_WRITE_DTYPE, FLOW_KEY_DTYPE, L1_DTYPE,
+                     CTRL_WRITE_DTYPE, FLOW_KEY_DTYPE, L1_DTYPE, PATCH_INFO_DTYPE,
+                     SEGMENT_INFO_DTYPE,
                      EGRESS_INFO_DTYPE, INGRESS_INFO_DTYPE, LAUNCH_INFO_DTYPE, NDP_DTYPE, RULE_DTYPE, RULE_INDEX_INFO_DTYPE,
                      RULE_STAT_DTYPE)
 
@@ -50,6 +51,7 @@ INGRESS_REF, INGRESS_WINDOW, INGRESS_FULL = 0, 1, 2   # UPE_INGRESS_REF / _WINDO
 # upe_gpu_latency_record (include/upe_gpu.h)
 LATENCY_BLOCK = 1024      # UPE_LATENCY_BLOCK: packets per workgroup pass of the histogram kernel
 CTRL_BLOCK = 1024         # UPE_CTRL_BLOCK: packets per workgroup of the control-write kernels
+PATCH_BLOCK = 256         # UPE_PATCH_BLOCK: records per workgroup of the neighbour-patch kernels
 
 
 # upe_tx_batch_fn: int (*)(void *user, const uint8_t *const *frames, const size_t *lens, int count)
@@ -155,6 +157,9 @@ def _load() -> ctypes.CDLL:
         "upe_gpu_resolve_keys": (I, [P, P, P, SZ, P, P]),
         "upe_gpu_ctrl_writes": (I, [P, P, P, SZ, P, SZ, P, P]),
         "upe_gpu_process_segmented": (I, [P, P, P, P, SZ, P, SZ, P, SZ, ctypes.c_int64, P, P]),
+        "upe_gpu_neigh_patch": (I, [P, P, SZ, P, P, P]),
+        "upe_gpu_process_segmented_resident": (I, [P, P, P, P, SZ, P, SZ, P, SZ, ctypes.c_int64, P,
+                                                   P]),
         "upe_gpu_process_emit": (I, [P, P, P, P, P, SZ, P]),
         "upe_gpu_process_emit_tx": (I, [P, P, P, P, P, P, P, SZ, P]),
         "upe_gpu_process_batches_emit": (I, [P, P, P, P, P, SZ, SZ, P]),
@@ -182,6 +187,8 @@ def _load() -> ctypes.CDLL:
         "upe_neigh_lookup_host": (I, [P, SZ, P, SZ, P, SZ, P]),
         "upe_ctrl_writes_host": (I, [P, P, SZ, P, SZ, P]),
         "upe_neigh_apply_writes": (I, [P, SZ, P, SZ, P, SZ, ctypes.c_int64, P]),
+        "upe_neigh_patch_host": (I, [P, P, SZ, P, P]),
+        "upe_neigh_image_lookup_host": (I, [P, P, SZ, P]),
         "upe_pcap_read": (I, [ctypes.c_char_p, P, SZ, P, SZ, P]),
         "upe_host_last_error": (ctypes.c_char_p, []),
         "upe_latency_init": (None, [P]),
@@ -231,7 +238,9 @@ EXPORTED = ("upe_gpu_last_error", "upe_gpu_device_count", "upe_gpu_local_cpus", 
             "upe_gpu_parse_keys", "upe_gpu_match_keys",
             "upe_neigh_compile", "upe_neigh_image_free", "upe_gpu_load_neigh_image",
             "upe_gpu_resolve_keys", "upe_neigh_lookup_host",
-            "upe_gpu_ctrl_writes", "upe_ctrl_writes_host", "upe_neigh_apply_writes")
+            "upe_gpu_ctrl_writes", "upe_ctrl_writes_host", "upe_neigh_apply_writes",
+            "upe_gpu_neigh_patch", "upe_neigh_patch_host", "upe_neigh_image_lookup_host",
+            "upe_gpu_process_segmented_resident")
 
 
 def _check(rc: int, what: str) -> None:
@@ -469,6 +478,20 @@ class GpuWorker:
             len(ndp), now, ctypes.byref(nw), stream or None), "upe_gpu_process_segmented")
         return nw.value
 
+    def process_segmented_resident(self, frames, desc, verdict, n: int, arp: np.ndarray,
+                                   ndp: np.ndarray, now: int = 0, stream=None) -> np.ndarray:
+        """upe_gpu_process_segmented_resident: process_segmented from the batch's records
+        (ctrl_writes), a write to an address the tables hold queued as a neigh_patch and only a
+        new address uploaded again.  Returns the SEGMENT_INFO_DTYPE record."""
+        assert arp.dtype == ARP_DTYPE and ndp.dtype == NDP_DTYPE
+        assert arp.flags.c_contiguous and ndp.flags.c_contiguous
+        info = np.zeros(1, SEGMENT_INFO_DTYPE)
+        _check(LIB.upe_gpu_process_segmented_resident(
+            self._ctx, _dev_ptr(frames), _dev_ptr(desc), _dev_ptr(verdict), n,
+            _np_ptr(arp) if len(arp) else None, len(arp), _np_ptr(ndp) if len(ndp) else None,
+            len(ndp), now, _np_ptr(info), stream or None), "upe_gpu_process_segmented_resident")
+        return info[0]
+
     def process_emit_tx(self, frames, desc, verdict, hdr, tx, tx_count, n: int,
                         stream=None) -> None:
         """upe_gpu_process_emit plus the egress list by 64-packet group (device buffers)."""
@@ -615,6 +638,16 @@ class GpuWorker:
             self.d2h(out.view(np.uint8).reshape(-1), writes)
             self.sync()
         return out, x[0]
+
+    def neigh_patch(self, writes, count: int, miss, info, stream=None) -> None:
+        """upe_gpu_neigh_patch: the records whose address the loaded snapshot holds rewrite that
+        slot's MAC on the device (neigh.patch is the same on the slot arrays, neigh_patch_host on
+        a NeighImage).  Device buffers: writes (count CTRL_WRITE_DTYPE records, 16-byte aligned),
+        miss (count uint32 or None: the missed records' ranks), info (32 bytes,
+        PATCH_INFO_DTYPE)."""
+        _check(LIB.upe_gpu_neigh_patch(self._ctx, _dev_ptr(writes) or None, count,
+                                       _dev_ptr(miss) or None, _dev_ptr(info) or None,
+                                       stream or None), "upe_gpu_neigh_patch")
 
     def sync(self, stream=None) -> None:
         _check(LIB.upe_gpu_sync(self._ctx, stream or None), "upe_gpu_sync")
@@ -790,6 +823,31 @@ def neigh_apply_writes(arp, ndp, writes: np.ndarray, now: int) -> int:
                                   ctypes.byref(applied)) != 0:
         raise UpeGpuError(f"upe_neigh_apply_writes: {LIB.upe_host_last_error().decode()}")
     return applied.value
+
+
+def neigh_patch_host(image: "NeighImage", writes: np.ndarray):
+    """upe_neigh_patch_host: the records applied to a compiled snapshot (in place) where it holds
+    their address; (the missed records' ranks, the PATCH_INFO_DTYPE record)."""
+    w = np.ascontiguousarray(writes, CTRL_WRITE_DTYPE)
+    miss = np.full(max(len(w), 1), 0xEEEEEEEE, np.uint32)
+    info = np.zeros(1, PATCH_INFO_DTYPE)
+    if LIB.upe_neigh_patch_host(image.ptr, _np_ptr(w) if len(w) else None, len(w), _np_ptr(miss),
+                                _np_ptr(info)) != 0:
+        raise UpeGpuError(f"upe_neigh_patch_host: {LIB.upe_gpu_last_error().decode()}")
+    m = int(info["missed"][0])
+    assert (miss[m:] == 0xEEEEEEEE).all(), "written past the missed ranks"
+    return miss[:m].copy(), info[0]
+
+
+def neigh_image_lookup_host(image: "NeighImage", keys: np.ndarray) -> np.ndarray:
+    """upe_neigh_image_lookup_host: what a context that has loaded the image answers; uint64 per
+    key (FLOW_KEY_DTYPE) in upe_gpu_resolve_keys' format."""
+    k = np.ascontiguousarray(keys, dtype=FLOW_KEY_DTYPE)
+    out = np.full(len(k), 0xA7A7A7A7A7A7A7A7, np.uint64)
+    if LIB.upe_neigh_image_lookup_host(image.ptr, _np_ptr(k) if len(k) else None, len(k),
+                                       _np_ptr(out) if len(k) else None) != 0:
+        raise UpeGpuError(f"upe_neigh_image_lookup_host: {LIB.upe_gpu_last_error().decode()}")
+    return out
 
 
 def pcap_read(path: str):

@@ -74,6 +74,12 @@ CTRL_WRITE_DTYPE = np.dtype({"names": ["index", "kind", "zero0", "mac_off", "mac
 CTRL_INFO_DTYPE = np.dtype([("ctrl", "<u8"), ("writes", "<u8"), ("stored", "<u8"),
                             ("first_write", "<u8")])
 CW_ARP, CW_NDP = 4, 6        # UPE_CW_ARP / UPE_CW_NDP
+# upe_neigh_patch_info_t (upe_gpu_neigh_patch) and upe_segment_info_t
+# (upe_gpu_process_segmented_resident)
+PATCH_INFO_DTYPE = np.dtype([("records", "<u8"), ("patched", "<u8"), ("missed", "<u8"),
+                             ("first_miss", "<u8")])
+SEGMENT_INFO_DTYPE = np.dtype([("writes", "<u8"), ("patched", "<u8"), ("rebuilds", "<u8"),
+                               ("ctrl", "<u8")])
 # pktbuf_t (reference include/pktbuf.h:8-14; upe_pktbuf_t, 2064 bytes)
 PKTBUF_DATA = 2048
 PKTBUF_DTYPE = np.dtype([("timestamp", "<u8"), ("len", "<u8"), ("data", "u1", (PKTBUF_DATA,))])

@@ -71,3 +71,41 @@ def resolve_keys(arp, ndp, keys) -> np.ndarray:
     slot_words = np.ascontiguousarray(ndp["ip"]).reshape(-1, 16).view("<u4").reshape(-1, 4)
     out[is6] = _probe(home, w6, slot_words, ndp["valid"] != 0, _mac_words(ndp["mac"]))
     return out
+
+
+def patch(arp, ndp, writes):
+    """upe_gpu_neigh_patch restated on the slot arrays: the records (CTRL_WRITE_DTYPE, in rank
+    order) whose address the probe above reaches before the batch — arp_get_mac of ip bytes 0-3 for
+    kind 4, ndp_get_mac of the 16 bytes for kind 6 — rewrite the MAC of the slot that answers, the
+    last one aimed at a slot staying; every other record (an address no probe reaches, a family
+    without slots, another kind) is missed and changes nothing.  A refresh moves nothing, so
+    "reached before the batch" is "reached when the record's turn comes".  update_at is not
+    modelled.  Returns (arp, ndp, miss, info): patched copies of the arrays, the missed records'
+    ranks ascending (uint32), and (records, patched, missed, first_miss), first_miss 2^64 - 1
+    where nothing is missed."""
+    arp = (np.zeros(0, ARP_DTYPE) if arp is None else np.asarray(arp, ARP_DTYPE)).copy()
+    ndp = (np.zeros(0, NDP_DTYPE) if ndp is None else np.asarray(ndp, NDP_DTYPE)).copy()
+    w = np.asarray(writes).ravel()
+    n = len(w)
+    ip = np.ascontiguousarray(w["ip"]).reshape(n, 16)
+    words = ip.view("<u4").reshape(n, 4)
+    is4, is6 = w["kind"] == 4, w["kind"] == 6
+    # the slot that answers, as the probe's answer: slot + 1, 0 = not reached
+    slot = np.zeros(n, np.uint64)
+    a4 = words[is4, 0]
+    slot[is4] = _probe(a4, a4[:, None], np.ascontiguousarray(arp["ip"])[:, None],
+                       arp["valid"] != 0, np.arange(1, len(arp) + 1, dtype=np.uint64))
+    w6 = words[is6]
+    home = w6[:, 0] ^ w6[:, 1] ^ w6[:, 2] ^ w6[:, 3] if len(w6) else np.zeros(0, np.uint32)
+    slot_words = np.ascontiguousarray(ndp["ip"]).reshape(-1, 16).view("<u4").reshape(-1, 4)
+    slot[is6] = _probe(home, w6, slot_words, ndp["valid"] != 0,
+                       np.arange(1, len(ndp) + 1, dtype=np.uint64))
+    held = slot != 0
+    # in rank order: numpy's fancy assignment keeps the last of equal indexes
+    for t, fam in ((arp, is4), (ndp, is6)):
+        r = np.nonzero(fam & held)[0]
+        if len(r):
+            t["mac"][(slot[r] - 1).astype(np.int64)] = w["mac"][r]
+    miss = np.nonzero(~held)[0].astype(np.uint32)
+    first = int(miss[0]) if len(miss) else (1 << 64) - 1
+    return arp, ndp, miss, (n, n - len(miss), len(miss), first)
