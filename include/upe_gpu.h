@@ -1059,6 +1059,110 @@ int upe_gpu_process_segmented_resident(upe_gpu_ctx_t *ctx, uint8_t *d_frames,
                                        upe_ndp_entry_t *ndp, size_t ndp_capacity, int64_t now,
                                        upe_segment_info_t *info, void *stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Release order: what happens to every buffer of a classified batch afterwards               */
+/* ------------------------------------------------------------------------------------------ */
+/* worker_main (reference src/worker.c:280-303) frees the buffer of a dropped or consumed packet
+ * at that packet's exit from process_packet, in packet order (src/worker.c:97, 123, 135, 151, 170,
+ * 209, 252), queues a forwarded packet's buffer in tx_bufs[] (src/worker.c:240-243) and frees the
+ * queue, in queue order, after the burst's tx_send_batch (src/worker.c:287-303); an ARP request it
+ * answers goes out through tx_send before its buffer is freed (src/worker.c:51, then :123).  The
+ * reference pool is a LIFO stack behind a thread-local cache (src/pktbuf.c), so the order of the
+ * frees is the order of every later pktbuf_alloc.  upe_gpu_release_order builds that order for a
+ * classified batch resident in GPU memory (csrc/upe_release.hip); upe_release_flush makes the
+ * reference's calls from the lists, without looking at a verdict word.
+ *
+ * Bursts: either a fixed size (d_burst_first == NULL: burst b is packets [b * burst, min((b + 1) *
+ * burst, n)), 1 <= burst <= UPE_TX_BATCH_MAX, nb ignored; the form upe_tx_flush takes), or an
+ * offset array on the device (d_burst_first[0 .. nb]: burst b is [first[b], first[b + 1])), for a
+ * worker whose ring pops vary in size.  The array is valid when first[0] == 0, first[nb] == n and
+ * every burst holds 1 to UPE_TX_BATCH_MAX packets.  info.bad_bursts counts the violated conditions:
+ * one for first[0] != 0, one for first[nb] != n, one per burst b whose first[b + 1] - first[b]
+ * (modulo 2^32) is not in 1 .. UPE_TX_BATCH_MAX.  When it is nonzero *d_info is still written in
+ * full (the counts over the verdicts do not depend on bursts) and NO other output is touched; the
+ * call cannot see a device array before launching, so this is not a return value.
+ *
+ * Order.  For burst b = [s, e) with r packets whose verdict code is not UPE_V_FWD:
+ *   d_order[s .. s + r)   those packets' positions, ascending: process_packet's frees
+ *   d_order[s + r .. e)   the forwarded packets' positions, ascending: tx_bufs[], which is the
+ *                         burst's tx_send_batch argument order and the frees after it
+ *   d_burst_fwd[b]        e - s - r
+ *   d_handle[k]           d_slot[d_order[k]] (both given, or neither)
+ *   d_reply[0 .. replies) the positions whose verdict has UPE_VF_ARP_REPLY, ascending over the
+ *                         whole batch; nothing at or past d_reply + replies is written
+ * Only the code of a verdict word decides forwarded / consumed / dropped and only the flag bit
+ * decides reply: hand-made words are valid input, as for upe_gpu_compact.  The forwarded ranges of
+ * d_order, concatenated over the bursts, are exactly upe_gpu_compact(..., UPE_V_FWD, ...)'s list.
+ *
+ * Asynchronous on `stream` (NULL: the context's), ordered like a launch, at most three launches;
+ * scratch lives in the context, so a context's calls are queued one after another.  Counters, rule_stats,
+ * the latency histogram, the tables and upe_gpu_launch_info are untouched and no launch is counted.
+ * n == 0 zeroes *d_info with first_reply = UINT64_MAX and launches nothing.  -1
+ * (upe_gpu_last_error()) before any launch: a NULL context or d_info; NULL d_verdict, d_order or
+ * d_burst_fwd with n > 0; exactly one of d_slot / d_handle; d_burst_first == NULL with burst 0 or
+ * above UPE_TX_BATCH_MAX; d_burst_first given with nb == 0 && n > 0 or nb > n; n above 2^32 - 1 -
+ * UPE_RELEASE_BLOCK.
+ * UPE_RELEASE_BLOCK: packets per workgroup of the kernels (batch sizes around it are where tests
+ * look). */
+#define UPE_RELEASE_BLOCK 1024
+typedef struct {            /* device, 64 bytes, every byte written */
+    uint64_t packets;       /* n */
+    uint64_t bursts;        /* nb, or ceil(n / burst) in the fixed form */
+    uint64_t forwarded;     /* verdict code UPE_V_FWD */
+    uint64_t consumed;      /* code UPE_V_CONSUMED */
+    uint64_t dropped;       /* every other code */
+    uint64_t replies;       /* UPE_VF_ARP_REPLY set */
+    uint64_t first_reply;   /* position of the first, or UINT64_MAX */
+    uint64_t bad_bursts;    /* violated conditions of the offset array (0 in the fixed form) */
+} upe_release_info_t;
+
+int upe_gpu_release_order(upe_gpu_ctx_t *ctx, const uint32_t *d_verdict, size_t n,
+                          const uint32_t *d_burst_first, /* nb + 1 offsets, or NULL */
+                          size_t nb, uint32_t burst,     /* with NULL: fixed size, nb ignored */
+                          const uint32_t *d_slot,        /* n handles, optional */
+                          uint32_t *d_order,             /* n */
+                          uint32_t *d_handle,            /* n; given iff d_slot is */
+                          uint32_t *d_burst_fwd,         /* one per burst */
+                          uint32_t *d_reply,             /* n, optional */
+                          upe_release_info_t *d_info, void *stream);
+
+/* upe_gpu_release_order's exact host twin (upe_host.c): the same arguments on host arrays, the
+ * same bytes in order, handle, burst_fwd, reply[0 .. replies) and *info, nothing else written when
+ * bad_bursts is nonzero.  No GPU needed.  0 / -1 (upe_host_last_error()) for the same arguments. */
+int upe_release_order_host(const uint32_t *verdict, size_t n, const uint32_t *burst_first,
+                           size_t nb, uint32_t burst, const uint32_t *slot, uint32_t *order,
+                           uint32_t *handle, uint32_t *burst_fwd, uint32_t *reply,
+                           upe_release_info_t *info);
+
+/* The reference worker's calls from those lists, copied to the host.  Per burst b = [s, e), in
+ * order, with f = h_burst_fwd[b] and r = e - s - f:
+ *   1. send_one(frame, len) for each reply position inside the burst, ascending;
+ *   2. release(handles of h_order[s .. s + r)) in one call, skipped when r == 0;
+ *   3. when f > 0: one send() of the frames of h_order[s + r .. e) (pointers h_frames + offset,
+ *      lengths from h_desc; arguments and accounting as upe_tx_flush), then release() of their
+ *      handles.
+ * A handle is h_handle[k], or h_order[k] itself when h_handle is NULL.  release() stands for
+ * pktbuf_free of each handle in the order given.
+ * The one regrouping against the reference: a reply's tx_send moves ahead of the frees of the
+ * earlier packets of its burst.  It stays before its own buffer's free and before the burst's
+ * tx_send_batch, and the sequence of frees and the sequence of sends are each the reference's own.
+ * Everything is checked before the first callback (all or nothing): -1 (upe_host_last_error())
+ * with no call made for a NULL argument that is needed, a bad burst description (a fixed size of 0
+ * or above UPE_TX_BATCH_MAX; an offset array that is not valid, nb == 0 with n > 0, nb > n), an
+ * h_burst_fwd[b] above its burst's size, an h_order entry outside its burst, or a reply list that
+ * does not ascend strictly or names a position >= n. */
+typedef struct {
+    int  (*send_one)(void *user, const uint8_t *frame, size_t len);      /* tx_send */
+    upe_tx_batch_fn send;                                                /* tx_send_batch */
+    void (*release)(void *user, const uint32_t *handles, size_t count);  /* pktbuf_free of each */
+} upe_release_ops_t;
+int upe_release_flush(const uint8_t *h_frames, const uint64_t *h_desc, const uint32_t *h_order,
+                      const uint32_t *h_handle /* NULL: h_order's values are the handles */,
+                      const uint32_t *h_burst_first, size_t nb, uint32_t burst, size_t n,
+                      const uint32_t *h_burst_fwd, const uint32_t *h_reply, size_t replies,
+                      const upe_release_ops_t *ops, void *user,
+                      uint64_t *forwarded, uint64_t *dropped);
+
 /* Wait for all work queued on the context's stream (or `stream`). */
 int upe_gpu_sync(upe_gpu_ctx_t *ctx, void *stream);
 
@@ -1260,6 +1364,7 @@ UPE_STATIC_ASSERT(offsetof(upe_ctrl_write_t, mac_off) == 6, "upe_ctrl_write_t.ma
 UPE_STATIC_ASSERT(offsetof(upe_ctrl_write_t, mac) == 8, "upe_ctrl_write_t.mac");
 UPE_STATIC_ASSERT(offsetof(upe_ctrl_write_t, ip) == 16, "upe_ctrl_write_t.ip");
 UPE_STATIC_ASSERT(sizeof(upe_ctrl_info_t) == 32, "upe_ctrl_info_t layout");
+UPE_STATIC_ASSERT(sizeof(upe_release_info_t) == 64, "upe_release_info_t layout");
 UPE_STATIC_ASSERT(sizeof(upe_latency_hist_t) == 96, "latency_histogram_t layout");
 UPE_STATIC_ASSERT(offsetof(upe_latency_hist_t, total_count) == 64, "latency_histogram_t.total_count");
 UPE_STATIC_ASSERT(offsetof(upe_latency_hist_t, min_ns) == 72, "latency_histogram_t.min_ns");

@@ -1,7 +1,8 @@
 // upe_ctx.h — the context (struct upe_gpu_ctx) and the few helpers every entry point of the
 // library uses, for the units that hold the host side of the extern "C" ABI: upe_gpu.hip (the
 // classify path, create / destroy, the loads), upe_rx.hip, upe_egress.hip, upe_ingress.hip,
-// upe_latency.hip, upe_ctrl.hip, upe_neigh_patch.hip, upe_hostpath.hip and upe_segment.hip.  Internal: not part of
+// upe_latency.hip, upe_ctrl.hip, upe_neigh_patch.hip, upe_release.hip, upe_hostpath.hip and
+// upe_segment.hip.  Internal: not part of
 // the ABI, and nothing declared here is exported.
 #ifndef UPE_CTX_H
 #define UPE_CTX_H
@@ -327,6 +328,7 @@ struct upe_gpu_ctx {
     DevBuf<uint8_t> in_scratch;           // upe_gpu_ingress_gather: tile table + meta (upe_ingress.hip)
     DevBuf<uint8_t> cw_scratch;           // upe_gpu_ctrl_writes: tile table + words (upe_ctrl.hip)
     DevBuf<uint8_t> np_scratch;           // upe_gpu_neigh_patch: tile table + words (upe_neigh_patch.hip)
+    DevBuf<uint8_t> rl_scratch;           // upe_gpu_release_order: tile table + bitmaps (upe_release.hip)
     DevBuf<uint32_t> np_owner;            // its owner word per index slot, ARP then NDP: zero between calls
     DevBuf<unsigned long long> ring_wg;   // ring launches: per-batch counters + time origin
     // the latency histogram (upe_gpu_latency_record, upe_latency.hip): replicas of the 12 words

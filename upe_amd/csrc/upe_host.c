@@ -24,6 +24,9 @@
  *                       batch, as records: the host equivalent of upe_gpu_ctrl_writes.
  *   upe_neigh_apply_writes arp_update / ndp_update (src/arp_table.c:26-53,
  *                       src/ndp_table.c:39-65) of those records on the slot arrays.
+ *   upe_release_order_host the order in which worker_main frees a classified batch's buffers
+ *                       (src/worker.c:280-303): the host equivalent of upe_gpu_release_order.
+ *   upe_release_flush   worker_main's tx_send, tx_send_batch and pktbuf_free calls from those lists.
  */
 #define _GNU_SOURCE
 #include <arpa/inet.h>
@@ -440,6 +443,151 @@ int upe_tx_flush_packed(const uint8_t *h_out, const uint64_t *h_out_desc,
         if (sent > c) sent = c;
         if (forwarded) *forwarded += (uint64_t)sent;
         if (dropped) *dropped += (uint64_t)(c - sent);
+    }
+    return 0;
+}
+
+/* ---- release order ----------------------------------------------------------------------- */
+
+/* The burst description both release functions take: -1 for one that no call accepts. */
+static int release_bursts_ok(const char *who, const uint32_t *first, size_t nb, uint32_t burst,
+                             size_t n) {
+    if (!first && (burst == 0 || burst > UPE_TX_BATCH_MAX))
+        return host_fail("%.0d%s: burst must be 1..UPE_TX_BATCH_MAX", 0, who);
+    if (first && ((nb == 0 && n > 0) || nb > n))
+        return host_fail("%.0d%s: an offset array describes 1..n bursts", 0, who);
+    if (n > 0xFFFFFFFFull - UPE_RELEASE_BLOCK)
+        return host_fail("%.0d%s: n must fit in 32 bits", 0, who);
+    return 0;
+}
+
+/* The violated conditions of an offset array (upe_release_info_t.bad_bursts). */
+static uint64_t release_bad_bursts(const uint32_t *first, size_t nb, size_t n) {
+    uint64_t bad = (first[0] != 0u) + (first[nb] != (uint32_t)n);
+    for (size_t b = 0; b < nb; b++)
+        if ((uint32_t)(first[b + 1] - first[b] - 1u) >= UPE_TX_BATCH_MAX) bad++;
+    return bad;
+}
+
+/* Burst b of n packets: [*s, *e). */
+static void release_burst(const uint32_t *first, uint32_t burst, size_t n, size_t b, size_t *s,
+                          size_t *e) {
+    if (first) {
+        *s = first[b];
+        *e = first[b + 1];
+    } else {
+        *s = b * burst;
+        *e = n - *s < burst ? n : *s + burst;
+    }
+}
+
+/* The frees of worker_main in their order (src/worker.c:280-303): per burst the buffers
+ * process_packet frees at its exits, then tx_bufs[]. */
+int upe_release_order_host(const uint32_t *verdict, size_t n, const uint32_t *burst_first,
+                           size_t nb, uint32_t burst, const uint32_t *slot, uint32_t *order,
+                           uint32_t *handle, uint32_t *burst_fwd, uint32_t *reply,
+                           upe_release_info_t *info) {
+    if (!info || (n && (!verdict || !order || !burst_fwd)))
+        return host_fail("upe_release_order_host: null argument%.0d%s", 0, "");
+    if ((slot == NULL) != (handle == NULL))
+        return host_fail("upe_release_order_host: slot and handle go together%.0d%s", 0, "");
+    if (release_bursts_ok("upe_release_order_host", burst_first, nb, burst, n) != 0) return -1;
+    upe_release_info_t x;
+    memset(&x, 0, sizeof x);
+    x.packets = n;
+    x.first_reply = UINT64_MAX;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t code = UPE_VERDICT_CODE(verdict[i]);
+        if (code == UPE_V_FWD) x.forwarded++;
+        else if (code == UPE_V_CONSUMED) x.consumed++;
+        else x.dropped++;
+        if (verdict[i] & UPE_VF_ARP_REPLY) {
+            if (x.replies++ == 0) x.first_reply = i;
+        }
+    }
+    if (n == 0) {
+        *info = x;
+        return 0;
+    }
+    x.bursts = burst_first ? nb : (n + burst - 1) / burst;
+    if (burst_first) x.bad_bursts = release_bad_bursts(burst_first, nb, n);
+    *info = x;
+    if (x.bad_bursts) return 0;   /* reported in *info; no other output is touched */
+    for (size_t b = 0; b < x.bursts; b++) {
+        size_t s, e;
+        release_burst(burst_first, burst, n, b, &s, &e);
+        size_t k = s;
+        for (size_t i = s; i < e; i++)
+            if (UPE_VERDICT_CODE(verdict[i]) != UPE_V_FWD) order[k++] = (uint32_t)i;
+        burst_fwd[b] = (uint32_t)(e - k);
+        for (size_t i = s; i < e; i++)
+            if (UPE_VERDICT_CODE(verdict[i]) == UPE_V_FWD) order[k++] = (uint32_t)i;
+    }
+    if (slot)
+        for (size_t k = 0; k < n; k++) handle[k] = slot[order[k]];
+    if (reply) {
+        size_t k = 0;
+        for (size_t i = 0; i < n; i++)
+            if (verdict[i] & UPE_VF_ARP_REPLY) reply[k++] = (uint32_t)i;
+    }
+    return 0;
+}
+
+/* worker_main's calls from the lists (src/worker.c:51 tx_send, :287-303 the flush and its frees),
+ * everything checked before the first one. */
+int upe_release_flush(const uint8_t *h_frames, const uint64_t *h_desc, const uint32_t *h_order,
+                      const uint32_t *h_handle, const uint32_t *h_burst_first, size_t nb,
+                      uint32_t burst, size_t n, const uint32_t *h_burst_fwd,
+                      const uint32_t *h_reply, size_t replies, const upe_release_ops_t *ops,
+                      void *user, uint64_t *forwarded, uint64_t *dropped) {
+    if (release_bursts_ok("upe_release_flush", h_burst_first, nb, burst, n) != 0) return -1;
+    if (n && (!h_frames || !h_desc || !h_order || !h_burst_fwd || !ops || !ops->send ||
+              !ops->release))
+        return host_fail("upe_release_flush: null argument%.0d%s", 0, "");
+    if (replies && (!h_reply || !ops || !ops->send_one))
+        return host_fail("upe_release_flush: replies without a list or send_one%.0d%s", 0, "");
+    if (n && h_burst_first && release_bad_bursts(h_burst_first, nb, n) != 0)
+        return host_fail("upe_release_flush: the offset array is not valid%.0d%s", 0, "");
+    for (size_t k = 0; k < replies; k++)
+        if (h_reply[k] >= n || (k && h_reply[k] <= h_reply[k - 1]))
+            return host_fail("upe_release_flush: reply list entry %d is out of order or range%s",
+                             (int)k, "");
+    const size_t bursts = n == 0 ? 0 : h_burst_first ? nb : (n + burst - 1) / burst;
+    for (size_t b = 0; b < bursts; b++) {
+        size_t s, e;
+        release_burst(h_burst_first, burst, n, b, &s, &e);
+        if (h_burst_fwd[b] > e - s)
+            return host_fail("upe_release_flush: burst %d forwards more than it holds%s", (int)b, "");
+        for (size_t k = s; k < e; k++)
+            if (h_order[k] < s || h_order[k] >= e)
+                return host_fail("upe_release_flush: order entry %d lies outside its burst%s",
+                                 (int)k, "");
+    }
+    const uint32_t *handles = h_handle ? h_handle : h_order;
+    const uint8_t *frames[UPE_TX_BATCH_MAX];
+    size_t lens[UPE_TX_BATCH_MAX];
+    size_t q = 0; /* the next reply */
+    for (size_t b = 0; b < bursts; b++) {
+        size_t s, e;
+        release_burst(h_burst_first, burst, n, b, &s, &e);
+        const size_t f = h_burst_fwd[b], r = e - s - f;
+        for (; q < replies && h_reply[q] < e; q++) { /* ascending and < n: inside [s, e) */
+            const uint64_t d = h_desc[h_reply[q]];
+            ops->send_one(user, h_frames + (d >> 16), (size_t)(d & 0xFFFFu));
+        }
+        if (r) ops->release(user, handles + s, r);
+        if (f == 0) continue; /* src/worker.c:287: no call for a burst that forwarded nothing */
+        for (size_t k = 0; k < f; k++) {
+            const uint64_t d = h_desc[h_order[s + r + k]];
+            frames[k] = h_frames + (d >> 16);
+            lens[k] = (size_t)(d & 0xFFFFu);
+        }
+        int sent = ops->send(user, frames, lens, (int)f);
+        if (sent < 0) sent = 0;
+        if (sent > (int)f) sent = (int)f;
+        if (forwarded) *forwarded += (uint64_t)sent;
+        if (dropped) *dropped += (uint64_t)((int)f - sent);
+        ops->release(user, handles + s + r, f);
     }
     return 0;
 }

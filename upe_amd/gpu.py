@@ -20,7 +20,7 @@ from .layout import (ARP_DTYPE, BATCH_INFO_DTYPE, COUNTERS_DTYPE, CTRL_INFO_DTYP
                      CTRL_WRITE_DTYPE, FLOW_KEY_DTYPE, L1_DTYPE, PATCH_INFO_DTYPE,
                      SEGMENT_INFO_DTYPE,
                      EGRESS_INFO_DTYPE, INGRESS_INFO_DTYPE, LAUNCH_INFO_DTYPE, NDP_DTYPE, RULE_DTYPE, RULE_INDEX_INFO_DTYPE,
-                     RULE_STAT_DTYPE)
+                     RELEASE_INFO_DTYPE, RULE_STAT_DTYPE)
 
 LIB_PATH = os.environ.get("UPE_GPU_LIB_DIAG") or os.path.join(
     os.path.dirname(os.path.abspath(__file__)), "libupe_gpu.so")  # override: diagnostic builds only
@@ -52,6 +52,7 @@ INGRESS_REF, INGRESS_WINDOW, INGRESS_FULL = 0, 1, 2   # UPE_INGRESS_REF / _WINDO
 LATENCY_BLOCK = 1024      # UPE_LATENCY_BLOCK: packets per workgroup pass of the histogram kernel
 CTRL_BLOCK = 1024         # UPE_CTRL_BLOCK: packets per workgroup of the control-write kernels
 PATCH_BLOCK = 256         # UPE_PATCH_BLOCK: records per workgroup of the neighbour-patch kernels
+RELEASE_BLOCK = 1024      # UPE_RELEASE_BLOCK: packets per workgroup of the release-order kernels
 
 
 # upe_tx_batch_fn: int (*)(void *user, const uint8_t *const *frames, const size_t *lens, int count)
@@ -83,6 +84,15 @@ class WorkerOps(ctypes.Structure):
                 ("arp_update", ARP_UPDATE_FN), ("ndp_update", NDP_UPDATE_FN),
                 ("load_neigh", CTX_FN), ("poll", POLL_FN), ("sync", CTX_FN),
                 ("publish", PUBLISH_FN), ("free_burst", FREE_BURST_FN)]
+
+
+# upe_release_ops_t callbacks: tx_send is TX_SEND_FN, tx_send_batch TX_BATCH_FN
+RELEASE_FN = ctypes.CFUNCTYPE(None, _VP, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t)
+
+
+class ReleaseOps(ctypes.Structure):
+    """upe_release_ops_t."""
+    _fields_ = [("send_one", TX_SEND_FN), ("send", TX_BATCH_FN), ("release", RELEASE_FN)]
 
 
 class WorkerCfg(ctypes.Structure):
@@ -160,6 +170,7 @@ def _load() -> ctypes.CDLL:
         "upe_gpu_neigh_patch": (I, [P, P, SZ, P, P, P]),
         "upe_gpu_process_segmented_resident": (I, [P, P, P, P, SZ, P, SZ, P, SZ, ctypes.c_int64, P,
                                                    P]),
+        "upe_gpu_release_order": (I, [P, P, SZ, P, SZ, ctypes.c_uint32, P, P, P, P, P, P, P]),
         "upe_gpu_process_emit": (I, [P, P, P, P, P, SZ, P]),
         "upe_gpu_process_emit_tx": (I, [P, P, P, P, P, P, P, SZ, P]),
         "upe_gpu_process_batches_emit": (I, [P, P, P, P, P, SZ, SZ, P]),
@@ -189,6 +200,9 @@ def _load() -> ctypes.CDLL:
         "upe_neigh_apply_writes": (I, [P, SZ, P, SZ, P, SZ, ctypes.c_int64, P]),
         "upe_neigh_patch_host": (I, [P, P, SZ, P, P]),
         "upe_neigh_image_lookup_host": (I, [P, P, SZ, P]),
+        "upe_release_order_host": (I, [P, SZ, P, SZ, ctypes.c_uint32, P, P, P, P, P, P]),
+        "upe_release_flush": (I, [P, P, P, P, P, SZ, ctypes.c_uint32, SZ, P, P, SZ,
+                                  ctypes.POINTER(ReleaseOps), P, P, P]),
         "upe_pcap_read": (I, [ctypes.c_char_p, P, SZ, P, SZ, P]),
         "upe_host_last_error": (ctypes.c_char_p, []),
         "upe_latency_init": (None, [P]),
@@ -240,7 +254,8 @@ EXPORTED = ("upe_gpu_last_error", "upe_gpu_device_count", "upe_gpu_local_cpus", 
             "upe_gpu_resolve_keys", "upe_neigh_lookup_host",
             "upe_gpu_ctrl_writes", "upe_ctrl_writes_host", "upe_neigh_apply_writes",
             "upe_gpu_neigh_patch", "upe_neigh_patch_host", "upe_neigh_image_lookup_host",
-            "upe_gpu_process_segmented_resident")
+            "upe_gpu_process_segmented_resident",
+            "upe_gpu_release_order", "upe_release_order_host", "upe_release_flush")
 
 
 def _check(rc: int, what: str) -> None:
@@ -649,6 +664,29 @@ class GpuWorker:
                                        _dev_ptr(miss) or None, _dev_ptr(info) or None,
                                        stream or None), "upe_gpu_neigh_patch")
 
+    # ---- release order ----
+    def release_order(self, verdict, n: int, order, burst_fwd, info, first=None, nb: int = 0,
+                      burst: int = 0, slot=None, handle=None, reply=None, stream=None) -> None:
+        """upe_gpu_release_order: the order in which the reference worker frees the buffers of a
+        classified device batch (release.order_host is the same on the host).  Bursts: first (nb + 1
+        uint32 offsets on the device) or a fixed size `burst`.  Device buffers: verdict (n uint32),
+        order (n uint32), burst_fwd (one uint32 per burst), info (64 bytes, RELEASE_INFO_DTYPE),
+        optional slot and handle (n uint32 each, together) and reply (n uint32)."""
+        _check(LIB.upe_gpu_release_order(self._ctx, _dev_ptr(verdict) or None, n,
+                                         _dev_ptr(first) or None, nb, burst,
+                                         _dev_ptr(slot) or None, _dev_ptr(order) or None,
+                                         _dev_ptr(handle) or None, _dev_ptr(burst_fwd) or None,
+                                         _dev_ptr(reply) or None, _dev_ptr(info) or None,
+                                         stream or None), "upe_gpu_release_order")
+
+    def fetch_release_info(self, info, stream=None) -> np.ndarray:
+        """The upe_release_info_t a release_order call wrote to the device (synchronises)."""
+        x = np.zeros(1, RELEASE_INFO_DTYPE)
+        self.sync(stream)
+        self.d2h(x, info)
+        self.sync()
+        return x[0]
+
     def sync(self, stream=None) -> None:
         _check(LIB.upe_gpu_sync(self._ctx, stream or None), "upe_gpu_sync")
 
@@ -1005,6 +1043,90 @@ def tx_flush_packed(out: np.ndarray, out_desc: np.ndarray, out_index: np.ndarray
     if bad:
         raise UpeGpuError(f"upe_tx_flush_packed: {bad[0]}")
     return batches, int(fwd.value), int(drp.value)
+
+
+RELEASE_POISON = 0xEEEEEEEE   # what release_order_host's arrays hold where the call wrote nothing
+
+
+def release_order_host(verdict: np.ndarray, first=None, burst: int = 0, slot=None,
+                       want_reply: bool = True, nb: int | None = None):
+    """upe_release_order_host over host arrays: (order, handle, burst_fwd, reply, info), each array
+    as the call left it over RELEASE_POISON — n entries (burst_fwd: one per burst) and 16 more
+    behind them that the call must not touch; handle is None without `slot`, reply without
+    want_reply.  first: nb + 1 uint32 offsets (nb: another count to pass), else the fixed size
+    `burst`."""
+    v = np.ascontiguousarray(verdict, np.uint32)
+    n = len(v)
+    f = None if first is None else np.ascontiguousarray(first, np.uint32)
+    if f is not None and nb is None:
+        nb = len(f) - 1
+    bursts = nb if f is not None else (n + burst - 1) // burst if burst else 0
+    sl = None if slot is None else np.ascontiguousarray(slot, np.uint32)
+    room = lambda k: np.full(k + 16, RELEASE_POISON, np.uint32)
+    order, bf = room(n), room(bursts)
+    handle = room(n) if sl is not None else None
+    reply = room(n) if want_reply else None
+    info = np.zeros(1, RELEASE_INFO_DTYPE)
+    if LIB.upe_release_order_host(_np_ptr(v) if n else None, n, None if f is None else _np_ptr(f),
+                                  nb or 0, int(burst), None if sl is None else _np_ptr(sl),
+                                  _np_ptr(order), None if handle is None else _np_ptr(handle),
+                                  _np_ptr(bf), None if reply is None else _np_ptr(reply),
+                                  _np_ptr(info)) != 0:
+        raise UpeGpuError(f"upe_release_order_host: {LIB.upe_host_last_error().decode()}")
+    return order, handle, bf, reply, info[0]
+
+
+def release_flush(frames: np.ndarray, desc: np.ndarray, order, burst_fwd, first=None,
+                  burst: int = 0, handle=None, reply=None, sent_of=None, nb: int | None = None,
+                  n: int | None = None):
+    """upe_release_flush over host arrays: returns (events, forwarded, dropped), events = the
+    callbacks in call order, each one of
+      ("send_one", packet index, frame bytes)            tx_send of an answered ARP request
+      ("release", [handles])                             pktbuf_free of each, in order
+      ("send", packet indexes (int64 array), [frame bytes])   tx_send_batch, as tx_flush reports it
+    sent_of(count) -> frames the stand-in for sendmmsg reports sent (default: all)."""
+    frames = np.ascontiguousarray(frames)
+    desc = np.ascontiguousarray(desc, dtype=np.uint64)
+    n = int(desc.shape[0]) if n is None else n
+    order = np.ascontiguousarray(order, np.uint32)
+    bf = np.ascontiguousarray(burst_fwd, np.uint32)
+    f = None if first is None else np.ascontiguousarray(first, np.uint32)
+    if f is not None and nb is None:
+        nb = len(f) - 1
+    h = None if handle is None else np.ascontiguousarray(handle, np.uint32)
+    r = np.zeros(0, np.uint32) if reply is None else np.ascontiguousarray(reply, np.uint32)
+    base = frames.ctypes.data
+    index_of = {int(o): i for i, o in enumerate((desc >> np.uint64(16)).tolist())}
+    events = []
+
+    def send_one(user, fr, ln):
+        off = fr - base
+        events.append(("send_one", index_of[off], bytes(frames[off:off + ln])))
+        return 0
+
+    def send(user, fr, lens, count):
+        idx, data = [], []
+        for k in range(count):
+            off = fr[k] - base
+            idx.append(index_of[off])
+            data.append(bytes(frames[off:off + lens[k]]))
+        events.append(("send", np.array(idx, np.int64), data))
+        return count if sent_of is None else int(sent_of(count))
+
+    def release(user, handles, count):
+        events.append(("release", [int(handles[k]) for k in range(count)]))
+
+    ops = ReleaseOps(TX_SEND_FN(send_one), TX_BATCH_FN(send), RELEASE_FN(release))
+    fwd = ctypes.c_uint64(0)
+    drp = ctypes.c_uint64(0)
+    rc = LIB.upe_release_flush(_np_ptr(frames), _np_ptr(desc), _np_ptr(order),
+                               None if h is None else _np_ptr(h),
+                               None if f is None else _np_ptr(f), nb or 0, int(burst), n,
+                               _np_ptr(bf), _np_ptr(r) if len(r) else None, len(r),
+                               ctypes.byref(ops), None, ctypes.byref(fwd), ctypes.byref(drp))
+    if rc != 0:
+        raise UpeGpuError(f"upe_release_flush: {LIB.upe_host_last_error().decode()}")
+    return events, int(fwd.value), int(drp.value)
 
 
 class RuleImage:

@@ -80,6 +80,11 @@ PATCH_INFO_DTYPE = np.dtype([("records", "<u8"), ("patched", "<u8"), ("missed", 
                              ("first_miss", "<u8")])
 SEGMENT_INFO_DTYPE = np.dtype([("writes", "<u8"), ("patched", "<u8"), ("rebuilds", "<u8"),
                                ("ctrl", "<u8")])
+# upe_release_info_t (upe_gpu_release_order)
+RELEASE_INFO_DTYPE = np.dtype([("packets", "<u8"), ("bursts", "<u8"), ("forwarded", "<u8"),
+                               ("consumed", "<u8"), ("dropped", "<u8"), ("replies", "<u8"),
+                               ("first_reply", "<u8"), ("bad_bursts", "<u8")])
+TX_BATCH_MAX = 64            # UPE_TX_BATCH_MAX: the most packets a burst holds
 # pktbuf_t (reference include/pktbuf.h:8-14; upe_pktbuf_t, 2064 bytes)
 PKTBUF_DATA = 2048
 PKTBUF_DTYPE = np.dtype([("timestamp", "<u8"), ("len", "<u8"), ("data", "u1", (PKTBUF_DATA,))])
