@@ -27,6 +27,9 @@
 #include <stdint.h>
 
 #include "upe_ctx.h"
+#include "upe_scan.h"
+
+using namespace upe;
 
 namespace {
 
@@ -37,48 +40,11 @@ constexpr uint32_t kPer = kBlock / kThreads;   // packets per thread
 constexpr uint32_t kGroups = kBlock / 64;      // (round, wave) pairs of a tile: 64-packet groups
 constexpr uint32_t kScanThreads = 1024;        // tiles per step of the scan
 constexpr uint32_t kScanWaves = kScanThreads / 64;
-constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kNaBit = 1u << 24;          // word: the record's address is the NA's target
 // The walk's proof bound: every iteration advances off by at least 8 and off + 2 <= len <= 65535.
 constexpr uint32_t kWalkMax = 8190;
 static_assert(kBlock % kThreads == 0 && kGroups == kPer * kWaves, "tile shape");
 static_assert(78u + 8u * kWalkMax + 2u > 65535u, "the bound covers every frame length");
-
-__device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
-
-template <typename T>
-__device__ __forceinline__ T wave_excl(T x, int lane, T& total) {
-    T s = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T y = __shfl_up(s, d);
-        if (lane >= d) s += y;
-    }
-    total = __shfl(s, 63);
-    return s - x;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d);
-    return x;
-}
-
-__device__ __forceinline__ uint32_t wave_min(uint32_t x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const uint32_t y = __shfl_xor(x, d);
-        x = y < x ? y : x;
-    }
-    return x;
-}
-
-// The word holding frame bytes first .. first + 3, with the bytes at or past len zeroed.
-__device__ __forceinline__ uint32_t keep(uint32_t w, uint32_t len, uint32_t first) {
-    if (len >= first + 4u) return w;
-    if (len <= first) return 0u;
-    return w & ((1u << (8u * (len - first))) - 1u);
-}
 
 // Frame i: its first byte (a 64-bit offset: byte_offset goes up to 2^36) and its length.
 __device__ __forceinline__ const uint8_t* frame_of(const uint8_t* frames, uint64_t d, uint32_t& len) {
@@ -181,18 +147,8 @@ __global__ void __launch_bounds__(kScanThreads) upe_ctrl_scan(
             const uint32_t x = fwr[t];
             fw = x < fw ? x : fw;
         }
-        uint32_t ww;
-        uint32_t ex = wave_excl(w, lane, ww);
-        __syncthreads();   // the step before has read s_ww (and the shared words are set)
-        if (lane == 0) s_ww[wave] = ww;
-        __syncthreads();
-        uint32_t all = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kScanWaves; ++j) {
-            const uint32_t x = s_ww[j];
-            if (j < wave) ex += x;
-            all += x;
-        }
+        uint32_t all;   // (the first step's barriers also order the shared words set above)
+        const uint32_t ex = block_excl(w, lane, wave, s_ww, all);
         if (t < T) wex[t] = carry + ex;
         carry += all;
     }
@@ -272,32 +228,23 @@ __global__ void __launch_bounds__(kThreads) upe_ctrl_write(
     }
 }
 
-uint32_t tiles_of(uint32_t n) { return (uint32_t)(((uint64_t)n + kBlock - 1) / kBlock); }
-
 struct Tab {
     uint32_t *nctrl, *nwr, *fwr, *wex, *word;
 };
 
-Tab tab_of(void* scratch, uint32_t T) {
+// The scratch of one call over n packets in T tiles (n > 0).
+Tab layout(Carver& c, uint32_t T, uint32_t n) {
     const size_t tp = ((size_t)T + 3u) & ~(size_t)3u;
     Tab t;
-    t.nctrl = static_cast<uint32_t*>(scratch);
-    t.nwr = t.nctrl + tp;
-    t.fwr = t.nwr + tp;
-    t.wex = t.fwr + tp;
-    t.word = t.wex + tp;
+    t.nctrl = c.take<uint32_t>(tp);
+    t.nwr = c.take<uint32_t>(tp);
+    t.fwr = c.take<uint32_t>(tp);
+    t.wex = c.take<uint32_t>(tp);
+    t.word = c.take<uint32_t>(n);
     return t;
 }
 
-// Bytes of scratch one call over n packets needs (n > 0).
-size_t scratch_bytes(uint32_t n) {
-    const size_t tp = ((size_t)tiles_of(n) + 3u) & ~(size_t)3u;
-    return (4 * tp + (size_t)n) * sizeof(uint32_t);
-}
-
 }  // namespace
-
-using namespace upe;
 
 extern "C" int upe_gpu_ctrl_writes(upe_gpu_ctx_t* c, const uint8_t* d_frames,
                                    const uint64_t* d_desc, size_t n, upe_ctrl_write_t* d_writes,
@@ -309,15 +256,12 @@ extern "C" int upe_gpu_ctrl_writes(upe_gpu_ctx_t* c, const uint8_t* d_frames,
     if (n > 0xFFFFFFFFull - UPE_CTRL_BLOCK) return fail("n must fit in 32 bits");
     DEV_SCOPE(c->device);
     hipStream_t s = pick(c, stream);
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(d_info, 0, sizeof(upe_ctrl_info_t), s));
-        HIP_TRY(hipMemsetAsync(&d_info->first_write, 0xFF, sizeof(uint64_t), s));
-        return 0;
-    }
-    const size_t need = scratch_bytes((uint32_t)n);
+    if (n == 0) return empty_info(d_info, &upe_ctrl_info_t::first_write, s);
+    const uint32_t T = tiles_of((uint32_t)n, kBlock);
+    const size_t need = layout_bytes(layout, T, (uint32_t)n);
     if (c->cw_scratch.reserve(need, need + need / 4) != 0) return -1;
-    const uint32_t T = tiles_of((uint32_t)n);
-    const Tab t = tab_of(c->cw_scratch.p, T);
+    Carver mem(c->cw_scratch.p);
+    const Tab t = layout(mem, T, (uint32_t)n);
     hipLaunchKernelGGL(upe_ctrl_mark, dim3(T), dim3(kThreads), 0, s, d_frames, d_desc, (uint32_t)n,
                        t.word, t.nctrl, t.nwr, t.fwr);
     HIP_TRY(hipGetLastError());

@@ -1,5 +1,6 @@
 // upe_ctx.h — the context (struct upe_gpu_ctx) and the few helpers every entry point of the
-// library uses, for the units that hold the host side of the extern "C" ABI: upe_gpu.hip (the
+// library uses (owned device buffers, the carving of a stage's scratch, an empty batch's info,
+// timing events, stream order), for the units that hold the host side of the extern "C" ABI: upe_gpu.hip (the
 // classify path, create / destroy, the loads), upe_rx.hip, upe_egress.hip, upe_ingress.hip,
 // upe_latency.hip, upe_ctrl.hip, upe_neigh_patch.hip, upe_release.hip, upe_hostpath.hip and
 // upe_segment.hip.  Internal: not part of
@@ -114,6 +115,46 @@ struct DevBuf {
     operator T*() const { return p; }
     T* operator->() const { return p; }
 };
+
+// One allocation carved into arrays: take<T>(count) is the next address aligned for T (or to
+// `align` bytes, a power of two, where a kernel loads wider than T) and moves past count elements;
+// bytes() is what the takes so far need.  Over a null base nothing is dereferenced, so a stage's
+// one layout function gives both its scratch size and, over the allocation, its pointers.  The
+// base is a hipMalloc'ed address: aligned for every type taken.
+struct Carver {
+    uintptr_t base;
+    size_t used = 0;
+    explicit Carver(void* p) : base(reinterpret_cast<uintptr_t>(p)) {}
+    template <class T>
+    T* take(size_t count, size_t align = alignof(T)) {
+        used = (used + align - 1) & ~(align - 1);
+        T* p = reinterpret_cast<T*>(base + used);
+        used += count * sizeof(T);
+        return p;
+    }
+    size_t bytes() const { return used; }
+};
+// The bytes a stage's `layout(Carver&, args...)` takes: the layout over no memory.
+template <class Layout, class... Args>
+size_t layout_bytes(Layout layout, Args... args) {
+    Carver none(nullptr);
+    layout(none, args...);
+    return none.bytes();
+}
+
+// Workgroups ("tiles") of `block` items that cover n of them.
+inline uint32_t tiles_of(uint32_t n, uint32_t block) {
+    return (uint32_t)(((uint64_t)n + block - 1) / block);
+}
+
+// What an empty batch leaves in a stage's info, queued on `s`: zero, but for the word that names
+// the first packet of a kind, which says "none" (UINT64_MAX).
+template <class Info>
+int empty_info(Info* d_info, uint64_t Info::*first, hipStream_t s) {
+    HIP_TRY(hipMemsetAsync(d_info, 0, sizeof(Info), s));
+    HIP_TRY(hipMemsetAsync(&(d_info->*first), 0xFF, sizeof(uint64_t), s));
+    return 0;
+}
 
 // The timing events of one diagnostic call (the _timed entry points), destroyed with it: N - 2
 // around the call's N - 3 passes, then a pair around a yardstick copy.

@@ -29,6 +29,9 @@
 #include <stdint.h>
 
 #include "upe_ctx.h"
+#include "upe_scan.h"
+
+using namespace upe;
 
 namespace {
 
@@ -39,34 +42,12 @@ constexpr uint32_t kPer = kBlock / kThreads;    // packets per thread
 constexpr uint32_t kGroups = kBlock / 64;       // (round, wave) pairs of a tile: 64-packet groups
 constexpr uint32_t kScanThreads = kBlock;       // one thread per packet of the tile with the cut
 constexpr uint32_t kScanWaves = kScanThreads / 64;
-constexpr uint32_t kNone = 0xFFFFFFFFu;
 static_assert(kBlock % kThreads == 0 && kGroups == kPer * kWaves, "tile shape");
 static_assert(kScanThreads <= 1024, "one workgroup");
 
-__device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
 __device__ __forceinline__ bool is_fwd(uint32_t v) { return (v & 0xFu) == (uint32_t)UPE_V_FWD; }
 __device__ __forceinline__ uint32_t quads_of(uint64_t d) {
     return ((uint32_t)(d & 0xFFFFu) + 15u) >> 4;
-}
-
-// Exclusive prefix of x over the wave's lanes, and the wave's total.
-template <typename T>
-__device__ __forceinline__ T wave_excl(T x, int lane, T& total) {
-    T s = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T y = __shfl_up(s, d);
-        if (lane >= d) s += y;
-    }
-    total = __shfl(s, 63);
-    return s - x;
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d);
-    return x;
 }
 
 __global__ void __launch_bounds__(kThreads) upe_egress_size(const uint64_t* desc,
@@ -126,29 +107,9 @@ __global__ void __launch_bounds__(kScanThreads) upe_egress_scan(
         const uint32_t t = c0 + tid;
         const uint32_t c = t < T ? cnt[t] : 0u;
         const uint64_t q = t < T ? (uint64_t)qs[t] : 0ull;
-        uint32_t wc;
-        uint64_t wq;
-        uint32_t ec = wave_excl(c, lane, wc);
-        uint64_t eq = wave_excl(q, lane, wq);
-        __syncthreads();   // the step before has read s_wc / s_wq (and s_cut is set)
-        if (lane == 0) {
-            s_wc[wave] = wc;
-            s_wq[wave] = wq;
-        }
-        __syncthreads();
-        uint32_t all_c = 0;
-        uint64_t all_q = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kScanWaves; ++j) {
-            const uint32_t x = s_wc[j];
-            const uint64_t y = s_wq[j];
-            if (j < wave) {
-                ec += x;
-                eq += y;
-            }
-            all_c += x;
-            all_q += y;
-        }
+        uint32_t ec = c, all_c;
+        uint64_t eq = q, all_q;   // (the first step's barriers also order s_cut, set above)
+        block_excl(ec, eq, lane, wave, s_wc, s_wq, all_c, all_q);
         ec += carry_c;
         eq += carry_q;
         if (t < T) {
@@ -227,13 +188,6 @@ __device__ __forceinline__ void patch(uint4& x, const uint4 r, uint32_t j) {
     } else {
         x.y = (x.y & 0xFFFF00FFu) | ((r.w & 0xFFu) << 8);
     }
-}
-
-// Zero the bytes of a quad from byte `rem` on (0 < rem < 16).
-__device__ __forceinline__ uint32_t keep(uint32_t w, uint32_t rem, uint32_t first) {
-    if (rem >= first + 4u) return w;
-    if (rem <= first) return 0u;
-    return w & ((1u << (8u * (rem - first))) - 1u);
 }
 
 template <bool kHdr>
@@ -316,7 +270,7 @@ __global__ void __launch_bounds__(kThreads) upe_egress_copy(
                 uint4 x = frames[(size_t)sq + j];
                 if (kHdr && j < 2u) patch(x, rec[m >> 16], j);
                 const uint32_t rem = (m & 0xFFFFu) - 16u * j;   // > 0: the frame reaches quad j
-                if (rem < 16u) {
+                if (rem < 16u) {   // the quad's bytes from `rem` on are zeroed
                     x.x = keep(x.x, rem, 0u);
                     x.y = keep(x.y, rem, 4u);
                     x.z = keep(x.z, rem, 8u);
@@ -328,27 +282,20 @@ __global__ void __launch_bounds__(kThreads) upe_egress_copy(
     }
 }
 
-uint32_t tiles_of(uint32_t n) { return (uint32_t)(((uint64_t)n + kBlock - 1) / kBlock); }
-
 struct Tab {
     uint64_t* qex;
     uint32_t *cnt, *qs, *cex;
 };
 
-Tab tab_of(void* scratch, uint32_t T) {
+// The scratch of one pack over T tiles.
+Tab layout(Carver& c, uint32_t T) {
     const size_t tp = ((size_t)T + 1u) & ~(size_t)1u;
     Tab t;
-    t.qex = static_cast<uint64_t*>(scratch);
-    t.cnt = reinterpret_cast<uint32_t*>(t.qex + tp);
-    t.qs = t.cnt + tp;
-    t.cex = t.qs + tp;
+    t.qex = c.take<uint64_t>(tp);   // the 64-bit column first
+    t.cnt = c.take<uint32_t>(tp);
+    t.qs = c.take<uint32_t>(tp);
+    t.cex = c.take<uint32_t>(tp);
     return t;
-}
-
-// Bytes of scratch one pack of n packets needs (n > 0).
-size_t upe_egress_scratch_bytes(uint32_t n) {
-    const size_t tp = ((size_t)tiles_of(n) + 1u) & ~(size_t)1u;
-    return tp * (sizeof(uint64_t) + 3 * sizeof(uint32_t));
 }
 
 // Queue the three passes on `s`, with the arguments as egress_pack has checked them.  hdr NULL:
@@ -358,8 +305,9 @@ hipError_t upe_egress_launch(const uint8_t* frames, const uint64_t* desc, const 
                              uint64_t out_bytes, uint64_t* out_desc, uint32_t* out_index,
                              upe_egress_info_t* info, void* scratch, hipStream_t s,
                              hipEvent_t* ev) {
-    const uint32_t T = tiles_of(n);
-    const Tab t = tab_of(scratch, T);
+    const uint32_t T = tiles_of(n, kBlock);
+    Carver mem(scratch);
+    const Tab t = layout(mem, T);
     const uint64_t cap = out_bytes >> 4;
     const uint4* f4 = reinterpret_cast<const uint4*>(frames);
     const uint4* h4 = reinterpret_cast<const uint4*>(hdr);
@@ -383,8 +331,6 @@ hipError_t upe_egress_launch(const uint8_t* frames, const uint64_t* desc, const 
     if ((e = hipGetLastError()) != hipSuccess) return e;
     return ev ? hipEventRecord(ev[3], s) : hipSuccess;
 }
-
-using namespace upe;
 
 // The egress batch builder (reference src/worker.c:240-243, 287-303: the frames queued for
 // tx_send_batch, in order).  ev: NULL, or four events recorded before the size pass and after each
@@ -413,7 +359,7 @@ int egress_pack(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_des
     const uintptr_t fr_end = alloc_end(d_frames, fr + 1);
     if (out < fr_end && fr < out + (out_bytes ? out_bytes : 1))
         return fail("d_out overlaps d_frames");
-    const size_t need = upe_egress_scratch_bytes((uint32_t)n);
+    const size_t need = layout_bytes(layout, tiles_of((uint32_t)n, kBlock));
     if (c->eg_scratch.reserve(need, need + need / 4) != 0) return -1;
     HIP_TRY(upe_egress_launch(d_frames, d_desc, d_verdict, d_hdr, (uint32_t)n, d_out, out_bytes,
                               d_out_desc, d_out_index, d_info, c->eg_scratch.p, s, ev));

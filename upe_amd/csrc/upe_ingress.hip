@@ -37,6 +37,9 @@
 #include <stdint.h>
 
 #include "upe_ctx.h"
+#include "upe_scan.h"
+
+using namespace upe;
 
 namespace {
 
@@ -48,43 +51,12 @@ constexpr uint32_t kGroups = kBlock / 64;        // (round, wave) pairs of a til
 constexpr uint32_t kScanThreads = kBlock;        // one thread per packet of the tile with the cut
 constexpr uint32_t kScanWaves = kScanThreads / 64;
 constexpr uint32_t kWinQuads = UPE_HDR_WINDOW / 16;
-constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kMark = 1u << 16, kBad = 1u << 17;   // meta word bits above the length
 static_assert(kBlock % kThreads == 0 && kGroups == kPer * kWaves, "tile shape");
 static_assert(kScanThreads <= 1024, "one workgroup");
 static_assert(UPE_HDR_WINDOW % 16 == 0, "windows are whole quads");
 
-__device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
 __device__ __forceinline__ uint32_t quads_of(uint32_t meta) { return ((meta & 0xFFFFu) + 15u) >> 4; }
-
-// Exclusive prefix of x over the wave's lanes, and the wave's total.
-template <typename T>
-__device__ __forceinline__ T wave_excl(T x, int lane, T& total) {
-    T s = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T y = __shfl_up(s, d);
-        if (lane >= d) s += y;
-    }
-    total = __shfl(s, 63);
-    return s - x;
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d);
-    return x;
-}
-
-__device__ __forceinline__ uint32_t wave_min(uint32_t x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const uint32_t y = __shfl_xor(x, d);
-        x = y < x ? y : x;
-    }
-    return x;
-}
 
 // Byte j (0..15) of a quad.
 __device__ __forceinline__ uint32_t byte_of(const uint4& q, uint32_t j) {
@@ -92,12 +64,7 @@ __device__ __forceinline__ uint32_t byte_of(const uint4& q, uint32_t j) {
     return (w >> (8u * (j & 3u))) & 0xFFu;
 }
 
-// Zero the bytes of a quad from byte `rem` on (0 < rem < 16).
-__device__ __forceinline__ uint32_t keep(uint32_t w, uint32_t rem, uint32_t first) {
-    if (rem >= first + 4u) return w;
-    if (rem <= first) return 0u;
-    return w & ((1u << (8u * (rem - first))) - 1u);
-}
+// Zero the bytes of a quad from byte `rem` on (rem > 0).
 __device__ __forceinline__ void zero_tail(uint4& x, uint32_t rem) {
     if (rem < 16u) {
         x.x = keep(x.x, rem, 0u);
@@ -233,6 +200,9 @@ __global__ void __launch_bounds__(kScanThreads) upe_ingress_scan(
             fb = x < fb ? x : fb;
             fc = y < fc ? y : fc;
         }
+        // block_excl's step (upe_scan.h), written out: through the helper this kernel, the one
+        // with the most live values across the step, took 7 more VGPRs and measured 0.05-0.1 us
+        // slower than the form below (profiles/scan_share_ab.txt)
         uint32_t wc;
         uint64_t wq;
         uint32_t ec = wave_excl(c, lane, wc);
@@ -435,31 +405,24 @@ __global__ void __launch_bounds__(kThreads) upe_ingress_write(
     }
 }
 
-uint32_t tiles_of(uint32_t n) { return (uint32_t)(((uint64_t)n + kBlock - 1) / kBlock); }
-
 struct Tab {
     uint64_t* qex;
     uint32_t *nbad, *fbad, *nctrl, *fctrl, *qs, *cex, *meta;
 };
 
-Tab tab_of(void* scratch, uint32_t T) {
+// The scratch of one gather of n packets in T tiles (n > 0).
+Tab layout(Carver& c, uint32_t T, uint32_t n) {
     const size_t tp = ((size_t)T + 1u) & ~(size_t)1u;
     Tab t;
-    t.qex = static_cast<uint64_t*>(scratch);
-    t.nbad = reinterpret_cast<uint32_t*>(t.qex + tp);
-    t.fbad = t.nbad + tp;
-    t.nctrl = t.fbad + tp;
-    t.fctrl = t.nctrl + tp;
-    t.qs = t.fctrl + tp;
-    t.cex = t.qs + tp;
-    t.meta = t.cex + tp;
+    t.qex = c.take<uint64_t>(tp);   // the 64-bit column first
+    t.nbad = c.take<uint32_t>(tp);
+    t.fbad = c.take<uint32_t>(tp);
+    t.nctrl = c.take<uint32_t>(tp);
+    t.fctrl = c.take<uint32_t>(tp);
+    t.qs = c.take<uint32_t>(tp);
+    t.cex = c.take<uint32_t>(tp);
+    t.meta = c.take<uint32_t>(n);
     return t;
-}
-
-// Bytes of scratch one gather of n packets needs (n > 0).
-size_t upe_ingress_scratch_bytes(uint32_t n) {
-    const size_t tp = ((size_t)tiles_of(n) + 1u) & ~(size_t)1u;
-    return tp * (sizeof(uint64_t) + 6 * sizeof(uint32_t)) + (size_t)n * sizeof(uint32_t);
 }
 
 // Queue the passes on `s`, with the arguments as ingress_gather has checked them.  A pass that a
@@ -469,8 +432,9 @@ hipError_t upe_ingress_launch(const uint8_t* pool, uint64_t pool_bytes, uint64_t
                               uint64_t out_bytes, uint64_t* desc, uint64_t* timestamp,
                               uint32_t* ctrl, upe_ingress_info_t* info, void* scratch,
                               hipStream_t s, hipEvent_t* ev) {
-    const uint32_t T = tiles_of(n);
-    const Tab t = tab_of(scratch, T);
+    const uint32_t T = tiles_of(n, kBlock);
+    Carver mem(scratch);
+    const Tab t = layout(mem, T, n);
     const uint64_t nbuf = pool_bytes / stride;
     const bool full = mode == UPE_INGRESS_FULL;
     const uint64_t cap = full ? out_bytes >> 4 : ~0ull;
@@ -510,8 +474,6 @@ hipError_t upe_ingress_launch(const uint8_t* pool, uint64_t pool_bytes, uint64_t
     if ((e = hipGetLastError()) != hipSuccess) return e;
     return ev ? hipEventRecord(ev[3], s) : hipSuccess;
 }
-
-using namespace upe;
 
 // The ingress batch builder (reference src/worker.c:255-307 hands the worker pktbuf handles;
 // upe_worker.c gathers them per packet on the CPU).  ev: NULL, or four events recorded before the
@@ -567,7 +529,7 @@ int ingress_gather(upe_gpu_ctx_t* c, const uint8_t* pool, size_t pool_bytes, siz
         const uintptr_t out = reinterpret_cast<uintptr_t>(d_out);
         if (out < hi && lo < out + (out_bytes ? out_bytes : 1)) return fail("d_out overlaps the pool");
     }
-    const size_t need = upe_ingress_scratch_bytes((uint32_t)n);
+    const size_t need = layout_bytes(layout, tiles_of((uint32_t)n, kBlock), (uint32_t)n);
     if (c->in_scratch.reserve(need, need + need / 4) != 0) return -1;
     HIP_TRY(upe_ingress_launch(dpool, pool_bytes, stride, d_slot, (uint32_t)n, mode, d_out,
                                out_bytes, d_desc, d_timestamp, d_ctrl, d_info, c->in_scratch.p, s,

@@ -30,6 +30,9 @@
 
 #include "upe_ctx.h"
 #include "upe_neigh_lookup.h"
+#include "upe_scan.h"
+
+using namespace upe;
 
 namespace {
 
@@ -38,28 +41,6 @@ constexpr uint32_t kWaves = kBlock / 64;
 constexpr uint32_t kScanThreads = 1024;        // workgroups per step of the scan
 constexpr uint32_t kScanWaves = kScanThreads / 64;
 static_assert(kBlock % 64 == 0 && kBlock <= 1024, "a workgroup of whole waves");
-
-__device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
-
-__device__ __forceinline__ uint32_t wave_excl(uint32_t x, int lane, uint32_t& total) {
-    uint32_t s = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(s, d);
-        if (lane >= d) s += y;
-    }
-    total = __shfl(s, 63);
-    return s - x;
-}
-
-__device__ __forceinline__ uint32_t wave_min(uint32_t x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const uint32_t y = __shfl_xor(x, d);
-        x = y < x ? y : x;
-    }
-    return x;
-}
 
 // The snapshot as the kernels take it: the lookups' view, the slot arrays to write, and where the
 // NDP index's owner words begin.
@@ -131,18 +112,8 @@ __global__ void __launch_bounds__(kScanThreads) upe_patch_scan(
             const uint32_t x = fmiss[b];
             fm = x < fm ? x : fm;
         }
-        uint32_t ww;
-        uint32_t ex = wave_excl(w, lane, ww);
-        __syncthreads();   // the step before has read s_ww (and s_fm is set)
-        if (lane == 0) s_ww[wave] = ww;
-        __syncthreads();
-        uint32_t all = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kScanWaves; ++j) {
-            const uint32_t x = s_ww[j];
-            if (j < wave) ex += x;
-            all += x;
-        }
+        uint32_t all;   // (the first step's barriers also order s_fm, set above)
+        const uint32_t ex = block_excl(w, lane, wave, s_ww, all);
         if (b < T) mex[b] = carry + ex;
         carry += all;
     }
@@ -193,35 +164,27 @@ __global__ void __launch_bounds__(kBlock) upe_patch_commit(
     miss_out[pos] = i;   // pos < the call's misses
 }
 
-uint32_t blocks_of(uint32_t count) { return (uint32_t)(((uint64_t)count + kBlock - 1) / kBlock); }
-
 struct Tab {
     uint32_t *nmiss, *fmiss, *mex, *where;
 };
 
-Tab tab_of(void* scratch, uint32_t T) {
+// The scratch of one call over `count` records in T workgroups (count > 0).
+Tab layout(Carver& c, uint32_t T, uint32_t count) {
     const size_t tp = ((size_t)T + 3u) & ~(size_t)3u;
     Tab t;
-    t.nmiss = static_cast<uint32_t*>(scratch);
-    t.fmiss = t.nmiss + tp;
-    t.mex = t.fmiss + tp;
-    t.where = t.mex + tp;
+    t.nmiss = c.take<uint32_t>(tp);
+    t.fmiss = c.take<uint32_t>(tp);
+    t.mex = c.take<uint32_t>(tp);
+    t.where = c.take<uint32_t>(count);
     return t;
 }
-
-// Bytes of scratch one call over `count` records needs (count > 0).
-size_t scratch_bytes(uint32_t count) {
-    const size_t tp = ((size_t)blocks_of(count) + 3u) & ~(size_t)3u;
-    return (3 * tp + (size_t)count) * sizeof(uint32_t);
-}
-
-using namespace upe;
 
 // The call's launches, with what the context does around a change of its tables.
 int patch_launch(upe_gpu_ctx_t* c, const PatchTables& pt, const uint4* writes, uint32_t count,
                  uint32_t* d_miss, upe_neigh_patch_info_t* d_info, hipStream_t s) {
-    const uint32_t T = blocks_of(count);
-    const Tab t = tab_of(c->np_scratch.p, T);
+    const uint32_t T = tiles_of(count, kBlock);
+    Carver mem(c->np_scratch.p);
+    const Tab t = layout(mem, T, count);
     if (neigh_patching(c, s) != 0) return -1;
     hipLaunchKernelGGL(upe_patch_resolve, dim3(T), dim3(kBlock), 0, s, writes, count, pt,
                        c->np_owner.p, t.where, t.nmiss, t.fmiss);
@@ -246,16 +209,12 @@ extern "C" int upe_gpu_neigh_patch(upe_gpu_ctx_t* c, const upe_ctrl_write_t* d_w
     if (count > 0xFFFFFFFFull - UPE_PATCH_BLOCK) return fail("count must fit in 32 bits");
     DEV_SCOPE(c->device);
     hipStream_t s = pick(c, stream);
-    if (count == 0) {
-        HIP_TRY(hipMemsetAsync(d_info, 0, sizeof(upe_neigh_patch_info_t), s));
-        HIP_TRY(hipMemsetAsync(&d_info->first_miss, 0xFF, sizeof(uint64_t), s));
-        return 0;
-    }
+    if (count == 0) return empty_info(d_info, &upe_neigh_patch_info_t::first_miss, s);
     const NeighTable& n = c->neigh;
     const uint64_t arp_slots = n.arp_bits ? 1ull << n.arp_bits : 0ull;
     const uint64_t slots = arp_slots + (n.ndp_bits ? 1ull << n.ndp_bits : 0ull);
     if (slots >= kNone) return fail("neighbour index too large to patch");
-    const size_t need = scratch_bytes((uint32_t)count);
+    const size_t need = layout_bytes(layout, tiles_of((uint32_t)count, kBlock), (uint32_t)count);
     if (c->np_scratch.reserve(need, need + need / 4) != 0) return -1;
     if (slots > c->np_owner.cap) {   // a larger index since the last call: fresh zero words
         if (c->np_owner.reserve(slots, slots) != 0) return -1;

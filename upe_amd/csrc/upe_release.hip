@@ -39,6 +39,9 @@
 #include <stdint.h>
 
 #include "upe_ctx.h"
+#include "upe_scan.h"
+
+using namespace upe;
 
 namespace {
 
@@ -52,7 +55,6 @@ constexpr uint32_t kBits = (kGroups + 2) * 64;   // positions a bitmap holds: th
 constexpr uint32_t kStageRounds = (kBits + kThreads - 1) / kThreads;
 constexpr uint32_t kScanThreads = 1024;          // tiles per step of the scan
 constexpr uint32_t kScanWaves = kScanThreads / 64;
-constexpr uint32_t kNone = 0xFFFFFFFFu;
 static_assert(kBlock % kThreads == 0 && kGroups == kPer * kWaves, "tile shape");
 static_assert(UPE_TX_BATCH_MAX == 64, "a burst fits one ballot word");
 
@@ -63,33 +65,6 @@ struct Tab {
 
 __device__ __forceinline__ unsigned long long low_bits(uint32_t k) {   // k <= 64
     return k >= 64u ? ~0ull : (1ull << k) - 1ull;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d);
-    return x;
-}
-
-__device__ __forceinline__ uint32_t wave_min(uint32_t x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const uint32_t y = __shfl_xor(x, d);
-        x = y < x ? y : x;
-    }
-    return x;
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_excl(T x, int lane, T& total) {
-    T s = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T y = __shfl_up(s, d);
-        if (lane >= d) s += y;
-    }
-    total = __shfl(s, 63);
-    return s - x;
 }
 
 __global__ void __launch_bounds__(kThreads) upe_release_count(
@@ -185,18 +160,8 @@ __global__ void __launch_bounds__(kScanThreads) upe_release_scan(
             const uint32_t y = t.tfr[x];
             fr = y < fr ? y : fr;
         }
-        uint32_t rr;
-        uint32_t ex = wave_excl(r, lane, rr);
-        __syncthreads();   // the step before has read s_rr
-        if (lane == 0) s_rr[wave] = rr;
-        __syncthreads();
-        uint32_t all = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kScanWaves; ++j) {
-            const uint32_t y = s_rr[j];
-            if (j < wave) ex += y;
-            all += y;
-        }
+        uint32_t all;
+        const uint32_t ex = block_excl(r, lane, wave, s_rr, all);
         if (x < T) t.rex[x] = carry + ex;
         carry += all;
     }
@@ -342,36 +307,24 @@ __global__ void __launch_bounds__(kThreads) upe_release_write(
     }
 }
 
-uint32_t tiles_of(uint32_t n) { return (uint32_t)(((uint64_t)n + kBlock - 1) / kBlock); }
-
-size_t pad4(uint32_t T) { return ((size_t)T + 3u) & ~(size_t)3u; }
-
-Tab tab_of(void* scratch, uint32_t T) {
-    const size_t tp = pad4(T);
+// The scratch of one call over T tiles.
+Tab layout(Carver& c, uint32_t T) {
+    const size_t tp = ((size_t)T + 3u) & ~(size_t)3u;
     Tab t;
-    t.fwd = static_cast<unsigned long long*>(scratch);
-    t.rep = t.fwd + (size_t)T * kGroups;
-    t.tf = reinterpret_cast<uint32_t*>(t.rep + (size_t)T * kGroups);
-    t.tc = t.tf + tp;
-    t.tr = t.tc + tp;
-    t.tfr = t.tr + tp;
-    t.tb = t.tfr + tp;
-    t.rex = t.tb + tp;
-    t.b0 = t.rex + tp;
-    t.flag = t.b0 + tp;
+    t.fwd = c.take<unsigned long long>((size_t)T * kGroups);   // the ballot words: 64-bit, first
+    t.rep = c.take<unsigned long long>((size_t)T * kGroups);
+    t.tf = c.take<uint32_t>(tp);
+    t.tc = c.take<uint32_t>(tp);
+    t.tr = c.take<uint32_t>(tp);
+    t.tfr = c.take<uint32_t>(tp);
+    t.tb = c.take<uint32_t>(tp);
+    t.rex = c.take<uint32_t>(tp);
+    t.b0 = c.take<uint32_t>(tp);
+    t.flag = c.take<uint32_t>(4);
     return t;
 }
 
-// Bytes of scratch one call over n packets needs (n > 0).
-size_t scratch_bytes(uint32_t n) {
-    const uint32_t T = tiles_of(n);
-    return 2 * (size_t)T * kGroups * sizeof(unsigned long long) +
-           (7 * pad4(T) + 4) * sizeof(uint32_t);
-}
-
 }  // namespace
-
-using namespace upe;
 
 extern "C" int upe_gpu_release_order(upe_gpu_ctx_t* c, const uint32_t* d_verdict, size_t n,
                                      const uint32_t* d_burst_first, size_t nb, uint32_t burst,
@@ -389,15 +342,12 @@ extern "C" int upe_gpu_release_order(upe_gpu_ctx_t* c, const uint32_t* d_verdict
     if (n > 0xFFFFFFFFull - UPE_RELEASE_BLOCK) return fail("n must fit in 32 bits");
     DEV_SCOPE(c->device);
     hipStream_t s = pick(c, stream);
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(d_info, 0, sizeof(upe_release_info_t), s));
-        HIP_TRY(hipMemsetAsync(&d_info->first_reply, 0xFF, sizeof(uint64_t), s));
-        return 0;
-    }
-    const size_t need = scratch_bytes((uint32_t)n);
+    if (n == 0) return empty_info(d_info, &upe_release_info_t::first_reply, s);
+    const uint32_t T = tiles_of((uint32_t)n, kBlock);
+    const size_t need = layout_bytes(layout, T);
     if (c->rl_scratch.reserve(need, need + need / 4) != 0) return -1;
-    const uint32_t T = tiles_of((uint32_t)n);
-    const Tab t = tab_of(c->rl_scratch.p, T);
+    Carver mem(c->rl_scratch.p);
+    const Tab t = layout(mem, T);
     const uint64_t bursts = d_burst_first ? (uint64_t)nb : ((uint64_t)n + burst - 1) / burst;
     hipLaunchKernelGGL(upe_release_count, dim3(T), dim3(kThreads), 0, s, d_verdict, (uint32_t)n,
                        d_burst_first, (uint32_t)nb, T, t);

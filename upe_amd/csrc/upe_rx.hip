@@ -27,6 +27,9 @@
 #include <stdint.h>
 
 #include "upe_ctx.h"
+#include "upe_scan.h"
+
+using namespace upe;
 
 namespace {
 
@@ -41,8 +44,6 @@ constexpr uint32_t kScanPer = 8;               // tiles per lane and step of the
 constexpr uint32_t kScanRings = UPE_RX_RINGS_MAX / kScanWaves;   // rings per wave, at most
 static_assert(kRxBlock % kRxThreads == 0 && kRxSlots == 16, "tile shape");
 static_assert(UPE_RX_RINGS_MAX == 64 && UPE_RX_RINGS_MAX < kRxThreads, "one thread per ring");
-
-__device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
 
 // The lanes of the wave whose (live) packet has this lane's ring: one ballot per ring-id bit.
 // Called by every lane of the wave.
@@ -163,18 +164,6 @@ __global__ void __launch_bounds__(kRxThreads) upe_rx_hash(const uint8_t* frames,
     }
     __syncthreads();
     if (tid <= W) tab[(size_t)tid * tp + blockIdx.x] = s_cnt[tid];
-}
-
-// Exclusive prefix of x over the wave's lanes, and the wave's total.
-__device__ __forceinline__ uint32_t wave_excl(uint32_t x, int lane, uint32_t& total) {
-    uint32_t s = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(s, d);
-        if (lane >= d) s += y;
-    }
-    total = __shfl(s, 63);
-    return s - x;
 }
 
 // kScanPer entries of a column from tile t0 (a multiple of kScanPer, so they lie inside the
@@ -350,40 +339,47 @@ __global__ void __launch_bounds__(kRxThreads) upe_rx_scatter(uint32_t* ring, con
     }
 }
 
-uint32_t tiles_of(uint32_t n) { return (uint32_t)(((uint64_t)n + kRxBlock - 1) / kRxBlock); }
 uint32_t stride_of(uint32_t tiles) { return (tiles + kScanPer - 1) / kScanPer * kScanPer; }
 
-// Bytes of scratch one dispatch of n packets over `rings` rings needs (n > 0).
-size_t upe_rx_scratch_bytes(uint32_t n, uint32_t rings) {
-    return ((size_t)(rings + 2u) * stride_of(tiles_of(n)) + UPE_RX_RINGS_MAX) * sizeof(uint32_t);
+struct Tab {
+    uint32_t *tab, *base;
+};
+
+// The scratch of one dispatch over T tiles and `rings` rings.
+Tab layout(Carver& c, uint32_t T, uint32_t rings) {
+    Tab t;
+    // col_load / col_store move uint4: the table starts on 16 bytes, and every column does, a
+    // stride (a multiple of kScanPer entries) after the one before
+    t.tab = c.take<uint32_t>((size_t)(rings + 2u) * stride_of(T), sizeof(uint4));
+    t.base = c.take<uint32_t>(UPE_RX_RINGS_MAX);
+    return t;
 }
 
 // Queue the three passes on `s`, with the arguments as rx_dispatch has checked them.
 hipError_t upe_rx_launch(const uint8_t* frames, const uint64_t* desc, uint32_t n, uint32_t rings,
                          uint32_t rr, uint32_t* ring, uint32_t* flow_hash, uint32_t* index,
-                         uint64_t* desc_out, uint64_t* counts, uint32_t* scratch, hipStream_t s,
+                         uint64_t* desc_out, uint64_t* counts, void* scratch, hipStream_t s,
                          hipEvent_t* ev) {
-    const uint32_t T = tiles_of(n), tp = stride_of(T);
+    const uint32_t T = tiles_of(n, kRxBlock), tp = stride_of(T);
     uint32_t lg = 0;
     while ((1u << lg) < rings) ++lg;
-    uint32_t* base = scratch + (size_t)(rings + 2u) * tp;
+    Carver mem(scratch);
+    const Tab t = layout(mem, T, rings);
     hipError_t e;
     if (ev && (e = hipEventRecord(ev[0], s)) != hipSuccess) return e;
     hipLaunchKernelGGL(upe_rx_hash, dim3(T), dim3(kRxThreads), 0, s, frames, desc, n, lg, ring,
-                       flow_hash, scratch, tp);
+                       flow_hash, t.tab, tp);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (ev && (e = hipEventRecord(ev[1], s)) != hipSuccess) return e;
-    hipLaunchKernelGGL(upe_rx_scan, dim3(1), dim3(kScanThreads), 0, s, scratch, T, tp, lg, rr, base,
+    hipLaunchKernelGGL(upe_rx_scan, dim3(1), dim3(kScanThreads), 0, s, t.tab, T, tp, lg, rr, t.base,
                        reinterpret_cast<unsigned long long*>(counts));
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (ev && (e = hipEventRecord(ev[2], s)) != hipSuccess) return e;
     hipLaunchKernelGGL(upe_rx_scatter, dim3(T), dim3(kRxThreads), 0, s, ring, desc, n, lg, rr,
-                       scratch, tp, base, index, desc_out);
+                       t.tab, tp, t.base, index, desc_out);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     return ev ? hipEventRecord(ev[3], s) : hipSuccess;
 }
-
-using namespace upe;
 
 // The RX thread's dispatch (reference src/rx_pcap.c:19-25,67-80).  ev: NULL, or four events
 // recorded before the hash pass and after each pass (tools/rx_dispatch_time.py).
@@ -404,11 +400,10 @@ int rx_dispatch(upe_gpu_ctx_t* c, const uint8_t* d_frames, const uint64_t* d_des
         HIP_TRY(hipMemsetAsync(d_counts, 0, (rings + 1) * sizeof(uint64_t), s));
         return 0;
     }
-    const size_t need = upe_rx_scratch_bytes((uint32_t)n, rings);
+    const size_t need = layout_bytes(layout, tiles_of((uint32_t)n, kRxBlock), rings);
     if (c->rx_scratch.reserve(need, need + need / 4) != 0) return -1;
     HIP_TRY(upe_rx_launch(d_frames, d_desc, (uint32_t)n, rings, rr_start & (rings - 1), d_ring,
-                          d_flow_hash, d_index, d_desc_out, d_counts,
-                          reinterpret_cast<uint32_t*>(c->rx_scratch.p), s, ev));
+                          d_flow_hash, d_index, d_desc_out, d_counts, c->rx_scratch.p, s, ev));
     return 0;
 }
 
