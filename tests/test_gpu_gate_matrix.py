@@ -1,14 +1,17 @@
 """GPU: the gate matrix (tests/gates.py) through every device parser.
 
-The device has four copies of parse_flow_key's gates (the classify fast path, general_path in
-the scan / tree kernels, general_path with its barrel shift in the tuple-space kernels, rx_parse)
-plus upe_ctrl_mark / upe_ctrl_gather; all load whole 16-byte quads and model a zero-filled pktbuf
-by masking.  Every other batch of the suite has zeros behind each frame, where a gate that forgot
-its length test still answers right.  Here the slots are filled with 0xFF, the shape's own
-untruncated bytes or random bytes, every shape appears at every length, and the expected value
-is always the restated oracle on the same poisoned buffer (tests/test_gate_matrix.py shows that
-it cannot see the fill).  The frame comparison covers the whole buffer, so every byte at or past
-a frame's len must still hold its fill afterwards.
+The device has one definition of parse_flow_key's gates (parse_key, csrc/upe_parse.h, which
+upe_parse_keys calls) and three written-out statements of it: rx_parse, upe_classify's fast
+path, and the L4 gate of general_path, which takes its L4 words from the header's selector (a
+select chain in the scan / tree kernels, a barrel shift in the tuple-space kernels); plus
+upe_ctrl_mark / upe_ctrl_gather.  All load whole 16-byte quads and model a zero-filled pktbuf by
+masking, or use no byte that a length test has not covered.  Every other batch of the suite has
+zeros behind each frame, where a gate that forgot its length test still answers right.  Here the
+slots are filled with 0xFF, the shape's own untruncated bytes or random bytes, every shape
+appears at every length, and the expected value is always the restated oracle on the same
+poisoned buffer (tests/test_gate_matrix.py shows that it cannot see the fill).  The frame
+comparison covers the whole buffer, so every byte at or past a frame's len must still hold its
+fill afterwards.
 
 One test places the frames at byte offsets around and above 2^32 (include/upe_gpu.h allows
 offsets below 2^36) and compares every consumer's output with the same call at offsets from 0."""

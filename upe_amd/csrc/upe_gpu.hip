@@ -78,6 +78,7 @@
 #include "upe_ctx.h"
 #include "upe_match.h"
 #include "upe_neigh_lookup.h"
+#include "upe_parse.h"
 #include "upe_plan.h"
 
 using namespace upe;
@@ -324,18 +325,7 @@ __device__ __forceinline__ uint32_t wave_reduce(uint32_t x) {
     return dpp_op<K>(dpp_op<K>(r0, r1), dpp_op<K>(r2, r3));
 }
 
-__device__ __forceinline__ uint32_t byte_of(uint32_t w, int k) { return (w >> (8 * k)) & 0xFFu; }
-__device__ __forceinline__ uint32_t at2(uint32_t hi, uint32_t lo) {   // dword at byte 4q+2
-    return __builtin_amdgcn_alignbit(hi, lo, 16);
-}
-// Mask of the bytes of dword j that lie below len (a zero-filled pktbuf reads 0 past len).
-__device__ __forceinline__ uint32_t len_mask(uint32_t len, int j) {
-    const uint32_t lo = 4u * (uint32_t)j;
-    return len >= lo + 4 ? 0xFFFFFFFFu : len <= lo ? 0u : (1u << (8 * (len - lo))) - 1u;
-}
-__device__ __forceinline__ uint32_t be16_lo(uint32_t x) {             // BE u16 in bytes 0,1
-    return ((x & 0xFFu) << 8) | ((x >> 8) & 0xFFu);
-}
+// (byte_of, at2, be16_lo and len_mask: upe_parse.h)
 // RFC 1071 fold of a sum of native-LE u16 words held as a sum of u32 (u32 = lo + hi * 2^16,
 // and 2^16 == 1 in one's-complement arithmetic), complemented: src/parser.c:137-169.
 __device__ __forceinline__ uint32_t csum_fold(unsigned long long sum) {
@@ -559,45 +549,13 @@ __device__ __forceinline__ void general_path(Port a, uint8_t* p, uint32_t len, P
                 r.s[0] = bswap32(at2(w[7], w[6]));                           // bytes 26..29
                 r.d[0] = bswap32(at2(w[8], w[7]));                           // bytes 30..33
                 const uint32_t l4len = len - 14 - hl;
-                // L4 starts at byte 14 + 4 * ihl = 4 * (ihl + 3) + 2, i.e. in word ihl + 3, and
-                // registers are not indexable: l4 words from w[ihl + 3 .. ihl + 7], and x0 =
-                // w[ihl + 3] (the checksum's last half word), selected by IHL
-                uint32_t l4w0 = 0, l4w1 = 0, l4w3 = 0, x0 = 0;
-                if constexpr (kBarrel) {
-                    // a four-stage barrel shift by ihl - 5 (31 selects; ihl < 5 fails the parse
-                    // above, so only shifts 0..10 matter).  Tuple-space kernels only: in the scan
-                    // kernels it measured slower for config B, whose waves never run this path
-                    // (24.5 -> 26.7 us, an allocation effect; profiles/r04/v4_wave_general_ab.txt)
-                    const uint32_t sh = ihl - 5u;
-                    const uint32_t m8 = (uint32_t)((int32_t)(sh << 28) >> 31);
-                    const uint32_t m4 = (uint32_t)((int32_t)(sh << 29) >> 31);
-                    const uint32_t m2 = (uint32_t)((int32_t)(sh << 30) >> 31);
-                    const uint32_t m1 = (uint32_t)((int32_t)(sh << 31) >> 31);
-                    uint32_t y[12], z[8], u[6], x[5];
-#pragma unroll
-                    for (int k = 0; k < 12; ++k)
-                        y[k] = 16 + k < 24 ? vsel(m8, w[16 + k < 24 ? 16 + k : 0], w[8 + k]) : w[8 + k];
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) z[k] = vsel(m4, y[k + 4], y[k]);
-#pragma unroll
-                    for (int k = 0; k < 6; ++k) u[k] = vsel(m2, z[k + 2], z[k]);
-#pragma unroll
-                    for (int k = 0; k < 5; ++k) x[k] = vsel(m1, u[k + 1], u[k]);
-                    l4w0 = at2(x[1], x[0]);
-                    l4w1 = at2(x[2], x[1]);
-                    l4w3 = at2(x[4], x[3]);
-                    x0 = x[0];
-                } else {
-#pragma unroll
-                    for (int h = 5; h <= 15; ++h) {
-                        if ((int)ihl == h) {
-                            l4w0 = at2(w[h + 4], w[h + 3]);
-                            l4w1 = at2(w[h + 5], w[h + 4]);
-                            l4w3 = at2(w[h + 7], w[h + 6]);
-                            x0 = w[h + 3];
-                        }
-                    }
-                }
+                // the L4 words and x0 = w[ihl + 3] (the checksum's last half word), selected by
+                // IHL (l4_select, upe_parse.h; kBarrel picks the selector)
+                const L4Words l = l4_select<kBarrel>(w, ihl);
+                const uint32_t l4w0 = l.w0, l4w1 = l.w1, l4w3 = l.w3, x0 = l.x0;
+                // the L4 gate, a second statement of l4_gate (upe_parse.h), here and for IPv6
+                // below: calling l4_gate, in every shape of parameters and result tried, changed
+                // the assembly of all upe_classify instantiations (profiles/parse_share_ab.txt)
                 if (r.proto == 17u) {
                     r.ok = l4len >= 8u;
                     r.sport = be16_lo(l4w0);
@@ -633,6 +591,7 @@ __device__ __forceinline__ void general_path(Port a, uint8_t* p, uint32_t len, P
             }
         } else if (is_v6 && len - 14 >= 40u) {
             // as the fast path: next header byte 20, addresses 22..53, L4 at byte 54
+            // (the L4 gate written out, as for IPv4 above)
             r.proto = byte_of(w[5], 0);
             r.s[0] = at2(w[6], w[5]);   r.s[1] = at2(w[7], w[6]);
             r.s[2] = at2(w[8], w[7]);   r.s[3] = at2(w[9], w[8]);
@@ -1077,6 +1036,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerSimd) upe_classify(Args a) {
 
         if (first) STAMP_VM(2);
         // ---- fast path (option-less IPv4 / IPv6) or general path, chosen per wave ----
+        // (the fast path specialises parse_key, upe_parse.h, for the two shapes it takes)
         const uint32_t e12 = w[3] & 0xFFFFu;          // bytes 12,13 (ethertype, byte-swapped)
         const bool fast4 = live && len >= 34u && e12 == 0x0008u && byte_of(w[3], 2) == 0x45u;
         const bool fast6 = live && len >= 54u && e12 == 0xDD86u;

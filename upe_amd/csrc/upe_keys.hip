@@ -14,9 +14,7 @@
 // upe_parse_keys reads a frame's first 96 bytes as 16-byte loads, only the chunks that begin below
 // len (the batch layout keeps UPE_FRAME_TAIL bytes readable behind every frame start), and clears
 // every byte at or past len in the loaded words before any gate looks at them: what it computes
-// is parse_flow_key over a zero-filled pktbuf holding the frame, and every gate that succeeds has
-// checked that the bytes it goes on to use lie below len.  96 bytes hold every byte the parser
-// reads: an IPv4 header of 60 bytes puts the TCP data-offset byte at 14 + 60 + 12 = 86.
+// is parse_flow_key (parse_key, upe_parse.h) over a zero-filled pktbuf holding the frame.
 //
 // upe_match_keys unpacks a record into the words upe_classify hands its matchers (upe_match.h:
 // key_k0 / key_k1 and the address words) and calls the matcher of the table's index kind: the
@@ -29,15 +27,12 @@
 #include "upe_ctx.h"
 #include "upe_key_tile.h"
 #include "upe_match.h"
+#include "upe_parse.h"
 
 namespace {
 
-// A flow key in registers.  Record words: 0 ip_ver (bytes 1-3 padding), 1-4 src_ip, 5-8 dst_ip,
-// 9 src_port | dst_port << 16, 10 protocol (bytes 41-43 padding).
-struct Key {
-    uint32_t ver, proto, sport, dport;
-    uint32_t s[4], d[4];
-};
+// A flow key (Key, upe_parse.h) as a record.  Record words: 0 ip_ver (bytes 1-3 padding), 1-4
+// src_ip, 5-8 dst_ip, 9 src_port | dst_port << 16, 10 protocol (bytes 41-43 padding).
 __device__ __forceinline__ void key_to_words(const Key& k, uint32_t (&w)[kKeyWords]) {
     w[0] = k.ver;
 #pragma unroll
@@ -62,85 +57,6 @@ __device__ __forceinline__ Key key_from_words(const uint32_t (&w)[kKeyWords]) {
     k.dport = w[9] >> 16;
     k.proto = w[10] & 0xFFu;
     return k;
-}
-
-__device__ __forceinline__ uint32_t byte_of(uint32_t w, int k) { return (w >> (8 * k)) & 0xFFu; }
-__device__ __forceinline__ uint32_t at2(uint32_t hi, uint32_t lo) {   // dword at byte 4q+2
-    return __builtin_amdgcn_alignbit(hi, lo, 16);
-}
-__device__ __forceinline__ uint32_t be16_lo(uint32_t x) {             // BE u16 in bytes 0,1
-    return ((x & 0xFFu) << 8) | ((x >> 8) & 0xFFu);
-}
-// Mask of the bytes of dword j that lie below len.
-__device__ __forceinline__ uint32_t len_mask(uint32_t len, int j) {
-    const uint32_t lo = 4u * (uint32_t)j;
-    return len >= lo + 4 ? 0xFFFFFFFFu : len <= lo ? 0u : (1u << (8 * (len - lo))) - 1u;
-}
-
-// parse_flow_key (reference src/parser.c:6-111) over the frame's first 96 bytes, w, zero at and
-// past len.  The gates in the reference's order (and general_path's, upe_gpu.hip): the Ethernet
-// header, the ethertype, the IP header's length, version and IHL, the protocol, the L4 header's
-// length (TCP: and its data offset).  false: the key is not to be used.
-__device__ __forceinline__ bool parse_key(const uint32_t (&w)[24], uint32_t len, Key& k) {
-    k.ver = k.proto = k.sport = k.dport = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) k.s[j] = k.d[j] = 0;
-    if (len < 14u) return false;                                        // parser.c:8-10
-    const uint32_t et = be16_lo(w[3]);                                  // bytes 12, 13
-    const uint32_t iplen = len - 14u;
-    uint32_t l4w0, l4w1, l4w3, l4len;   // L4 bytes 0-3, 4-7, 12-15
-    if (et == 0x0800u) {                                                // parser.c:18-44
-        const uint32_t vihl = byte_of(w[3], 2), ihl = vihl & 0xFu, hl = ihl * 4u;
-        if (iplen < 20u || (vihl >> 4) != 4u || hl < 20u || iplen < hl) return false;
-        k.ver = 4;
-        k.proto = byte_of(w[5], 3);                                     // byte 23
-        k.s[0] = bswap32(at2(w[7], w[6]));                              // bytes 26..29, host order
-        k.d[0] = bswap32(at2(w[8], w[7]));                              // bytes 30..33
-        l4len = iplen - hl;
-        // L4 starts at byte 14 + 4 * ihl, in word ihl + 3 at byte 2; registers are not indexable,
-        // so the words are selected by IHL (5..15 here)
-        l4w0 = l4w1 = l4w3 = 0;
-#pragma unroll
-        for (int h = 5; h <= 15; ++h) {
-            if ((int)ihl == h) {
-                l4w0 = at2(w[h + 4], w[h + 3]);
-                l4w1 = at2(w[h + 5], w[h + 4]);
-                l4w3 = at2(w[h + 7], w[h + 6]);
-            }
-        }
-    } else if (et == 0x86DDu) {                                         // parser.c:46-64
-        if (iplen < 40u) return false;
-        k.ver = 6;
-        k.proto = byte_of(w[5], 0);                                     // byte 20
-        k.s[0] = at2(w[6], w[5]);   k.s[1] = at2(w[7], w[6]);           // bytes 22..37, wire order
-        k.s[2] = at2(w[8], w[7]);   k.s[3] = at2(w[9], w[8]);
-        k.d[0] = at2(w[10], w[9]);  k.d[1] = at2(w[11], w[10]);         // bytes 38..53
-        k.d[2] = at2(w[12], w[11]); k.d[3] = at2(w[13], w[12]);
-        l4len = iplen - 40u;
-        l4w0 = at2(w[14], w[13]);                                       // L4 at byte 54
-        l4w1 = at2(w[15], w[14]);
-        l4w3 = at2(w[17], w[16]);
-    } else {
-        return false;                                                   // parser.c:66-68
-    }
-    if (k.proto == 17u) {                                               // UDP, parser.c:70-78
-        if (l4len < 8u) return false;
-        k.sport = be16_lo(l4w0);
-        k.dport = be16_lo(l4w0 >> 16);
-    } else if (k.proto == 6u) {                                         // TCP, parser.c:79-94
-        if (l4len < 20u) return false;
-        const uint32_t thl = (byte_of(l4w3, 0) >> 4) * 4u;
-        if (thl < 20u || l4len < thl) return false;
-        k.sport = be16_lo(l4w0);
-        k.dport = be16_lo(l4w0 >> 16);
-    } else if (k.proto == 1u) {                                         // ICMP, parser.c:95-105
-        if (l4len < 8u) return false;
-        k.sport = be16_lo(l4w1);                                        // id
-        k.dport = be16_lo(l4w0);                                        // type << 8 | code
-    } else {
-        return false;                                                   // parser.c:106-108
-    }
-    return true;
 }
 
 __global__ void __launch_bounds__(kThreads) upe_parse_keys(const uint8_t* __restrict__ frames,
