@@ -1038,6 +1038,84 @@ int upe_neigh_patch_host(upe_neigh_image_t *image, const upe_ctrl_write_t *write
 int upe_neigh_image_lookup_host(const upe_neigh_image_t *image, const upe_flow_key_t *keys,
                                 size_t n, uint64_t *mac);
 
+/* New neighbours learnt on the device (csrc/upe_neigh_learn.hip): the records applied to the LOADED
+ * snapshot, the ones for an address it does not hold included — arp_update (src/arp_table.c:26-53)
+ * and ndp_update (src/ndp_table.c:39-65) of a new address take the first free slot of the probe,
+ * which exists whenever the table has an invalid slot and every valid entry is one a probe
+ * reaches; the lookups of such a table do not depend on where in the index an entry lies, so the
+ * address may take any free candidate slot of the index (DESIGN.md §3 has the argument).
+ *
+ * What a snapshot carries for this, per family, from the slot array it was compiled from
+ * (upe_neigh_image_read): free — the invalid slots; insertable — every valid slot is one a probe
+ * reaches and the index has slots (bits != 0).  A context keeps the two free counts on the device
+ * beside the index; a learn counts them down, a load sets them.
+ * upe_neigh_compile_room: upe_neigh_compile with each index sized for its reachable addresses plus
+ * `room` more (the placement starts at 2^bits * 4 >= (n + room) * 5), so that a burst of new
+ * addresses finds free candidate slots; a family without reachable addresses and room > 0 gets a
+ * real index with no slot used.  room 0 / 0 gives upe_neigh_compile's image byte for byte.  NULL
+ * on error, as there; also for a room above 2^30.
+ *
+ * The result is that of this loop over the records in rank order (rank: position in d_writes),
+ * on the loaded index and free[family]:
+ *   1. a kind that is neither UPE_CW_ARP nor UPE_CW_NDP: deferred;
+ *   2. the address is held now (the index's own lookup hits): the six MAC bytes of the slot that
+ *      answers are rewritten — patched;
+ *   3. else the family is not insertable: deferred;
+ *   4. else free == 0: dropped (the reference's full table does nothing);
+ *   5. else the first of slot1, slot2, slot3 (csrc/upe_dev.h) whose used bit is clear takes the
+ *      address, the MAC and the used bit; free-- — inserted;
+ *   6. else (no candidate slot is free): deferred, free unchanged.
+ * d_defer[0 .. deferred) (optional) are the deferred ranks, ascending; nothing at or past d_defer +
+ * deferred is written; patched + inserted + dropped + deferred == records.  After a call with
+ * deferred > 0 the caller applies the records on the host and loads (upe_neigh_apply_writes, then
+ * upe_gpu_load_neigh), as after a patch's misses; the load supersedes the device state.  bits, seed
+ * and every slot no record is aimed at keep every bit; no index is rebuilt, nothing is uploaded.
+ * Stream order, derived state (the L1 entries stay; their agreement with the tables is asked
+ * again), counters and launch info: upe_gpu_neigh_patch's rules — nothing is counted.  One launch
+ * of its own: one workgroup takes UPE_LEARN_CHUNK records per step, in rank order, so no result
+ * depends on how workgroups are scheduled; then the launches of the derived state.
+ * count == 0 zeroes *d_info with first_defer = UINT64_MAX and launches nothing.  -1
+ * (upe_gpu_last_error()) before any launch: a NULL context; a NULL d_info; a NULL d_writes with
+ * count > 0; d_writes not 16-byte aligned; count above 2^32 - 1 - UPE_LEARN_CHUNK.
+ * UPE_LEARN_CHUNK: records per step (counts around it are where tests look). */
+#define UPE_LEARN_CHUNK 1024
+typedef struct {          /* device, 64 bytes, every byte written */
+    uint64_t records;     /* count */
+    uint64_t patched;     /* records that took step 2 */
+    uint64_t inserted;    /* records that took step 5 */
+    uint64_t dropped;     /* records that took step 4 */
+    uint64_t deferred;    /* records that took step 1, 3 or 6 */
+    uint64_t first_defer; /* rank of the first deferred record, or UINT64_MAX */
+    uint64_t arp_free;    /* free of the ARP family after the call */
+    uint64_t ndp_free;    /* free of the NDP family after the call */
+} upe_neigh_learn_info_t;
+typedef struct {          /* host, 32 bytes */
+    uint32_t arp_bits, arp_seed, ndp_bits, ndp_seed;   /* the indexes: 2^bits slots, 0 = none */
+    uint32_t arp_free, ndp_free;                       /* invalid slots of the compiled arrays */
+    uint32_t arp_insertable, ndp_insertable;           /* 0 / 1 */
+} upe_neigh_image_info_t;
+
+upe_neigh_image_t *upe_neigh_compile_room(const upe_arp_entry_t *arp, size_t arp_capacity,
+                                          const upe_ndp_entry_t *ndp, size_t ndp_capacity,
+                                          size_t arp_room, size_t ndp_room);
+int upe_gpu_neigh_learn(upe_gpu_ctx_t *ctx, const upe_ctrl_write_t *d_writes, size_t count,
+                        uint32_t *d_defer /* count entries, optional */,
+                        upe_neigh_learn_info_t *d_info, void *stream);
+
+/* upe_gpu_neigh_learn's exact host twin (csrc/upe_rules.cpp): the loop above, written out, on a
+ * compiled snapshot — the same index bytes and free counts in the image, the same bytes in
+ * defer[0 .. deferred) and *info (arp_update: src/arp_table.c:26-53, ndp_update:
+ * src/ndp_table.c:39-65).  No GPU needed.  0 / -1 (upe_gpu_last_error()): a NULL image or info,
+ * NULL writes with count > 0, count above 2^32 - 1 - UPE_LEARN_CHUNK.
+ * upe_neigh_image_read: what an image holds — *info (optional), and the index slot arrays into arp
+ * / ndp (each optional; 16 bytes per ARP slot, 32 per NDP slot, 2^bits slots, one zero slot where
+ * bits == 0), each copied only when its size in bytes is given exactly; -1 otherwise. */
+int upe_neigh_learn_host(upe_neigh_image_t *image, const upe_ctrl_write_t *writes, size_t count,
+                         uint32_t *defer /* count entries, optional */,
+                         upe_neigh_learn_info_t *info);
+int upe_neigh_image_read(const upe_neigh_image_t *image, upe_neigh_image_info_t *info,
+                         void *arp, size_t arp_bytes, void *ndp, size_t ndp_bytes);
+
 /* upe_gpu_process_segmented without a frame byte on the host (csrc/upe_segment.hip): the same
  * batch, arguments and outputs, bit for bit — verdict words, frames, counters, rule_stats, the L1
  * state and the caller's slot arrays (update_at included).  The batch's records come from
@@ -1364,6 +1442,8 @@ UPE_STATIC_ASSERT(offsetof(upe_ctrl_write_t, mac_off) == 6, "upe_ctrl_write_t.ma
 UPE_STATIC_ASSERT(offsetof(upe_ctrl_write_t, mac) == 8, "upe_ctrl_write_t.mac");
 UPE_STATIC_ASSERT(offsetof(upe_ctrl_write_t, ip) == 16, "upe_ctrl_write_t.ip");
 UPE_STATIC_ASSERT(sizeof(upe_ctrl_info_t) == 32, "upe_ctrl_info_t layout");
+UPE_STATIC_ASSERT(sizeof(upe_neigh_learn_info_t) == 64, "upe_neigh_learn_info_t layout");
+UPE_STATIC_ASSERT(sizeof(upe_neigh_image_info_t) == 32, "upe_neigh_image_info_t layout");
 UPE_STATIC_ASSERT(sizeof(upe_release_info_t) == 64, "upe_release_info_t layout");
 UPE_STATIC_ASSERT(sizeof(upe_latency_hist_t) == 96, "latency_histogram_t layout");
 UPE_STATIC_ASSERT(offsetof(upe_latency_hist_t, total_count) == 64, "latency_histogram_t.total_count");

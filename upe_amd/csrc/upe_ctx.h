@@ -2,7 +2,8 @@
 // library uses (owned device buffers, the carving of a stage's scratch, an empty batch's info,
 // timing events, stream order), for the units that hold the host side of the extern "C" ABI: upe_gpu.hip (the
 // classify path, create / destroy, the loads), upe_rx.hip, upe_egress.hip, upe_ingress.hip,
-// upe_latency.hip, upe_ctrl.hip, upe_neigh_patch.hip, upe_release.hip, upe_hostpath.hip and
+// upe_latency.hip, upe_ctrl.hip, upe_neigh_patch.hip, upe_neigh_learn.hip, upe_release.hip,
+// upe_hostpath.hip and
 // upe_segment.hip.  Internal: not part of
 // the ABI, and nothing declared here is exported.
 #ifndef UPE_CTX_H
@@ -376,6 +377,22 @@ struct upe_gpu_ctx {
     // of a upe_latency_hist_t, touched by nothing but the four latency calls
     DevBuf<unsigned long long> lat_hist;
     double cycles_per_ns = 0.0;           // upe_gpu_set_tsc: 0 until it succeeds once
+    // upe_gpu_neigh_learn's state beside the loaded snapshot (upe_neigh_learn.hip): what the
+    // loaded image says of each family {ARP, NDP} — its free count and whether it takes new
+    // addresses — set by a load; the free counts as the learns since that load left them live on
+    // the device (made by the first learn; a load needs no device work for them: the first learn
+    // after it takes the image's counts as arguments).
+    struct Learn {
+        uint32_t image_free[2] = {0, 0};
+        bool insertable[2] = {false, false};
+        bool on_device = false;           // `free` holds the counts (a learn ran since the load)
+        DevBuf<uint32_t> free;            // {ARP, NDP, 0, 0}
+        void loaded(const upe::NeighImage& im) {
+            image_free[0] = im.arp_free, image_free[1] = im.ndp_free;
+            insertable[0] = im.arp_insertable, insertable[1] = im.ndp_insertable;
+            on_device = false;
+        }
+    } learn;
 };
 
 namespace upe {

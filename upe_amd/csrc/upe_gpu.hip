@@ -2296,6 +2296,7 @@ int upe_gpu_load_neigh_image(upe_gpu_ctx_t* c, const upe_neigh_image_t* image) {
     if (c->last_stream) HIP_TRY(hipStreamSynchronize(c->last_stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->neigh = std::move(next);   // frees the old snapshot: nothing queued reads it any more
+    c->learn.loaded(image->im);   // (host state only: upe_gpu_neigh_learn's free counts start here)
     if (c->st && refresh(c) != 0) return -1;   // does the L1 state agree with the new tables?
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;

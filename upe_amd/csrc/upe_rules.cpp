@@ -22,12 +22,12 @@ namespace upe {
 
 // (upe_rules.h)
 int cuckoo3_place(const std::vector<uint32_t>& key, uint32_t& bits, uint32_t& seed,
-                  std::vector<int32_t>& slot) {
+                  std::vector<int32_t>& slot, size_t room) {
     const size_t n = key.size();
     slot.clear();
     bits = 0;
     seed = 0;
-    if (n == 0) return 0;
+    if (n + room == 0) return 0;
     // Equal keys share their three candidate slots under every seed and at every size: a fourth
     // can never be placed.  Fail now: the search below would try every seed at every size up to
     // 2^31 slots first (terabytes of slot-array clears) before it gave up.
@@ -38,7 +38,7 @@ int cuckoo3_place(const std::vector<uint32_t>& key, uint32_t& bits, uint32_t& se
             if (sorted[j] == sorted[j - 3]) return -1;
     }
     bits = 1;
-    while (((size_t)1 << bits) * 4 < n * 5) ++bits;
+    while (((size_t)1 << bits) * 4 < (n + room) * 5) ++bits;   // (n + room <= 2^31)
     for (; bits <= 31; ++bits) {
         const size_t m = (size_t)1 << bits;
         for (uint32_t attempt = 0; attempt < 64; ++attempt) {
@@ -104,7 +104,7 @@ std::vector<uint32_t> reachable(const E* e, size_t cap, Home home, Same same) {
 
 // (upe_rules.h)
 int build_neigh_image(const upe_arp_entry_t* arp, size_t arp_cap, const upe_ndp_entry_t* ndp,
-                      size_t ndp_cap, NeighImage& im) {
+                      size_t ndp_cap, NeighImage& im, size_t arp_room, size_t ndp_room) {
     const std::vector<uint32_t> arp_keep = reachable(
         arp, arp_cap, [](const upe_arp_entry_t& e) { return (size_t)e.ip; },
         [](const upe_arp_entry_t& a, const upe_arp_entry_t& b) { return a.ip == b.ip; });
@@ -125,8 +125,8 @@ int build_neigh_image(const upe_arp_entry_t* arp, size_t arp_cap, const upe_ndp_
         nkey[j] = fold_v6(nwords[j].data());
     }
     std::vector<int32_t> aslot, nslot;   // slot -> entry (index into *_keep), -1 empty
-    if (cuckoo3_place(akey, im.arp_bits, im.arp_seed, aslot) != 0 ||
-        cuckoo3_place(nkey, im.ndp_bits, im.ndp_seed, nslot) != 0)
+    if (cuckoo3_place(akey, im.arp_bits, im.arp_seed, aslot, arp_room) != 0 ||
+        cuckoo3_place(nkey, im.ndp_bits, im.ndp_seed, nslot, ndp_room) != 0)
         return fail("neighbour index: cuckoo placement failed (at most three reachable IPv6 "
                     "addresses may share one fold_v6)");
     im.arp.assign(aslot.size(), make_uint4(0, 0, 0, 0));
@@ -145,18 +145,27 @@ int build_neigh_image(const upe_arp_entry_t* arp, size_t arp_cap, const upe_ndp_
     }
     if (im.arp.empty()) im.arp.push_back(make_uint4(0, 0, 0, 0));   // keep a valid allocation
     if (im.ndp.empty()) im.ndp.resize(2, make_uint4(0, 0, 0, 0));
+    // what upe_gpu_neigh_learn needs to know of the arrays (capacities <= 2^30)
+    size_t avalid = 0, nvalid = 0;
+    for (size_t s = 0; s < arp_cap; ++s) avalid += arp[s].valid ? 1u : 0u;
+    for (size_t s = 0; s < ndp_cap; ++s) nvalid += ndp[s].valid ? 1u : 0u;
+    im.arp_free = (uint32_t)(arp_cap - avalid);
+    im.ndp_free = (uint32_t)(ndp_cap - nvalid);
+    im.arp_insertable = im.arp_bits != 0 && arp_keep.size() == avalid;
+    im.ndp_insertable = im.ndp_bits != 0 && ndp_keep.size() == nvalid;
     return 0;
 }
 
 // (upe_rules.h)
 int compile_neigh(const upe_arp_entry_t* arp, size_t arp_cap, const upe_ndp_entry_t* ndp,
-                  size_t ndp_cap, NeighImage& im) {
+                  size_t ndp_cap, NeighImage& im, size_t arp_room, size_t ndp_room) {
     auto pow2 = [](size_t x) { return x == 0 || (x & (x - 1)) == 0; };
     if (!pow2(arp_cap) || !pow2(ndp_cap))
         return fail("neighbour table capacity must be a power of two (arp_table_init)");
     if ((arp_cap && !arp) || (ndp_cap && !ndp)) return fail("null table");
     if (arp_cap > (1u << 30) || ndp_cap > (1u << 30)) return fail("table too large");
-    return build_neigh_image(arp, arp_cap, ndp, ndp_cap, im);
+    if (arp_room > (1u << 30) || ndp_room > (1u << 30)) return fail("room too large");
+    return build_neigh_image(arp, arp_cap, ndp, ndp_cap, im, arp_room, ndp_room);
 }
 
 }  // namespace upe
@@ -1169,6 +1178,122 @@ extern "C" UPE_EXPORT int upe_neigh_patch_host(upe_neigh_image_t* image,
     info->patched = count - missed;
     info->missed = missed;
     info->first_miss = first;
+    return 0;
+}
+
+// upe_neigh_compile with room for new addresses in each index (include/upe_gpu.h).
+extern "C" UPE_EXPORT upe_neigh_image_t* upe_neigh_compile_room(
+    const upe_arp_entry_t* arp, size_t arp_capacity, const upe_ndp_entry_t* ndp,
+    size_t ndp_capacity, size_t arp_room, size_t ndp_room) {
+    try {
+        auto* im = new upe_neigh_image;
+        if (compile_neigh(arp, arp_capacity, ndp, ndp_capacity, im->im, arp_room, ndp_room) != 0) {
+            delete im;
+            return nullptr;
+        }
+        return im;
+    } catch (const std::bad_alloc&) {
+        fail("out of memory (neighbour image)");
+        return nullptr;
+    }
+}
+
+// What an image holds (include/upe_gpu.h).
+extern "C" UPE_EXPORT int upe_neigh_image_read(const upe_neigh_image_t* image,
+                                               upe_neigh_image_info_t* info, void* arp,
+                                               size_t arp_bytes, void* ndp, size_t ndp_bytes) {
+    if (!image) return fail("null argument");
+    const NeighImage& im = image->im;
+    if ((arp && arp_bytes != im.arp.size() * sizeof(uint4)) ||
+        (ndp && ndp_bytes != im.ndp.size() * sizeof(uint4)))
+        return fail("slot array size does not match the image");
+    if (info)
+        *info = upe_neigh_image_info_t{im.arp_bits, im.arp_seed, im.ndp_bits, im.ndp_seed,
+                                       im.arp_free, im.ndp_free, im.arp_insertable ? 1u : 0u,
+                                       im.ndp_insertable ? 1u : 0u};
+    if (arp) memcpy(arp, im.arp.data(), arp_bytes);
+    if (ndp) memcpy(ndp, im.ndp.data(), ndp_bytes);
+    return 0;
+}
+
+// upe_gpu_neigh_learn's twin (include/upe_gpu.h; the kernel: upe_neigh_learn.hip): the contract's
+// loop as it stands there, one record after another on the image's index and free counts.
+// arp_update (reference src/arp_table.c:26-53) / ndp_update (src/ndp_table.c:39-65) of a held
+// address rewrite the MAC; of a new one they take a free slot when the table has one.
+extern "C" UPE_EXPORT int upe_neigh_learn_host(upe_neigh_image_t* image,
+                                               const upe_ctrl_write_t* writes, size_t count,
+                                               uint32_t* defer, upe_neigh_learn_info_t* info) {
+    if (!image || !info || (count && !writes)) return fail("null argument");
+    if (count > 0xFFFFFFFFull - UPE_LEARN_CHUNK) return fail("count must fit in 32 bits");
+    NeighImage& im = image->im;
+    uint64_t patched = 0, inserted = 0, dropped = 0, deferred = 0, first = ~0ull;
+    auto put_off = [&](size_t i) {
+        if (deferred == 0) first = i;
+        if (defer) defer[deferred] = (uint32_t)i;
+        ++deferred;
+    };
+    for (size_t i = 0; i < count; ++i) {
+        const upe_ctrl_write_t& w = writes[i];
+        const uint32_t lo = mac_lo(w.mac), hi = mac_hi(w.mac);
+        if (w.kind == UPE_CW_ARP) {
+            const uint32_t ip = le32(w.ip);
+            const uint32_t t = arp_slot_host(im, ip);
+            if (t != kNone) {
+                im.arp[t].y = lo;
+                im.arp[t].z = (im.arp[t].z & 0xFFFF0000u) | hi;
+                ++patched;
+            } else if (!im.arp_insertable) {
+                put_off(i);
+            } else if (im.arp_free == 0) {
+                ++dropped;
+            } else {
+                const uint32_t c[3] = {slot1(ip, im.arp_seed, im.arp_bits),
+                                       slot2(ip, im.arp_seed, im.arp_bits),
+                                       slot3(ip, im.arp_seed, im.arp_bits)};
+                int q = 0;
+                while (q < 3 && ((im.arp[c[q]].z >> 16) & 1u)) ++q;
+                if (q == 3) {
+                    put_off(i);
+                } else {
+                    im.arp[c[q]] = make_uint4(ip, lo, hi | (1u << 16), 0);
+                    --im.arp_free;
+                    ++inserted;
+                }
+            }
+        } else if (w.kind == UPE_CW_NDP) {
+            const uint32_t ip[4] = {le32(w.ip), le32(w.ip + 4), le32(w.ip + 8), le32(w.ip + 12)};
+            const uint32_t t = ndp_slot_host(im, ip);
+            if (t != kNone) {
+                uint4& m = im.ndp[2 * (size_t)t + 1];
+                m.x = lo;
+                m.y = (m.y & 0xFFFF0000u) | hi;
+                ++patched;
+            } else if (!im.ndp_insertable) {
+                put_off(i);
+            } else if (im.ndp_free == 0) {
+                ++dropped;
+            } else {
+                const uint32_t k = fold_v6(ip);
+                const uint32_t c[3] = {slot1(k, im.ndp_seed, im.ndp_bits),
+                                       slot2(k, im.ndp_seed, im.ndp_bits),
+                                       slot3(k, im.ndp_seed, im.ndp_bits)};
+                int q = 0;
+                while (q < 3 && ((im.ndp[2 * (size_t)c[q] + 1].y >> 16) & 1u)) ++q;
+                if (q == 3) {
+                    put_off(i);
+                } else {
+                    im.ndp[2 * (size_t)c[q]] = make_uint4(ip[0], ip[1], ip[2], ip[3]);
+                    im.ndp[2 * (size_t)c[q] + 1] = make_uint4(lo, hi | (1u << 16), 0, 0);
+                    --im.ndp_free;
+                    ++inserted;
+                }
+            }
+        } else {
+            put_off(i);
+        }
+    }
+    *info = upe_neigh_learn_info_t{count, patched, inserted, dropped, deferred, first,
+                                   im.arp_free, im.ndp_free};
     return 0;
 }
 

@@ -62,28 +62,36 @@ namespace upe {
 UPE_INTERNAL int build_image(const upe_rule_t* rules, size_t count, size_t cap, upe_rule_image& im);
 
 // Three-choice cuckoo placement of the neighbour indexes' keys (slot1 / slot2 / slot3): starts at
-// 2^bits >= 1.25 n slots, random-walk eviction, seeds tried, then doubles.  bits = 0 for no keys.
+// 2^bits >= 1.25 (n + room) slots, random-walk eviction, seeds tried, then doubles.  bits = 0 for
+// no keys and no room; no keys with room: 2^bits free slots under the first seed.
 // -1, at once, when more than three keys are equal (they share all three slots at every size).
 UPE_INTERNAL int cuckoo3_place(const std::vector<uint32_t>& key, uint32_t& bits, uint32_t& seed,
-                               std::vector<int32_t>& slot);
+                               std::vector<int32_t>& slot, size_t room = 0);
 
 // The neighbour snapshot a context looks up in (NeighIndex, upe_gpu.hip): each family's slot
 // array and its placement.  Host memory only; an empty family keeps one zero slot (bits 0).
 struct UPE_INTERNAL NeighImage {
     std::vector<uint4> arp, ndp;
     uint32_t arp_bits = 0, arp_seed = 0, ndp_bits = 0, ndp_seed = 0;
+    // For upe_gpu_neigh_learn, from the slot arrays compiled: their invalid slots, and whether
+    // every valid slot is one a probe reaches and the index has slots (bits != 0).
+    uint32_t arp_free = 0, ndp_free = 0;
+    bool arp_insertable = false, ndp_insertable = false;
 };
 
 // Build the snapshot of the reference's slot arrays (power-of-two capacities, or 0): the entries
-// a reference probe reaches, placed by cuckoo3_place.  0, or -1 (upe_gpu_last_error()).
+// a reference probe reaches, placed by cuckoo3_place with `room` more keys' worth of slots.  0, or
+// -1 (upe_gpu_last_error()).
 UPE_INTERNAL int build_neigh_image(const upe_arp_entry_t* arp, size_t arp_cap,
-                                   const upe_ndp_entry_t* ndp, size_t ndp_cap, NeighImage& im);
+                                   const upe_ndp_entry_t* ndp, size_t ndp_cap, NeighImage& im,
+                                   size_t arp_room = 0, size_t ndp_room = 0);
 
 // upe_gpu_load_neigh's and upe_neigh_compile's arguments checked (power-of-two capacities of at
-// most 2^30 slots, a table wherever there is a capacity), then build_neigh_image.  0, or -1
-// (upe_gpu_last_error()).
+// most 2^30 slots, a table wherever there is a capacity, rooms of at most 2^30), then
+// build_neigh_image.  0, or -1 (upe_gpu_last_error()).
 UPE_INTERNAL int compile_neigh(const upe_arp_entry_t* arp, size_t arp_cap,
-                               const upe_ndp_entry_t* ndp, size_t ndp_cap, NeighImage& im);
+                               const upe_ndp_entry_t* ndp, size_t ndp_cap, NeighImage& im,
+                               size_t arp_room = 0, size_t ndp_room = 0);
 
 }  // namespace upe
 

@@ -1,7 +1,7 @@
 // upe_scan.h — what the ordered-output stages share on the device: upe_rx.hip, upe_egress.hip,
 // upe_ingress.hip, upe_ctrl.hip, upe_neigh_patch.hip and upe_release.hip each mark per tile, scan
 // the tiles in one workgroup and write behind the prefix.  The wave-level primitives and the scan
-// workgroup's step are defined here once.  HIP units only; internal linkage (an unnamed namespace,
+// workgroup's step are defined here once; upe_neigh_learn.hip's one workgroup uses the step too.  HIP units only; internal linkage (an unnamed namespace,
 // as upe_match.h and upe_neigh_lookup.h), so each unit compiles its own copies into its kernels.
 #ifndef UPE_SCAN_H
 #define UPE_SCAN_H

@@ -18,7 +18,7 @@ import numpy as np
 
 from .layout import (ARP_DTYPE, BATCH_INFO_DTYPE, COUNTERS_DTYPE, CTRL_INFO_DTYPE,
                      CTRL_WRITE_DTYPE, FLOW_KEY_DTYPE, L1_DTYPE, PATCH_INFO_DTYPE,
-                     SEGMENT_INFO_DTYPE,
+                     SEGMENT_INFO_DTYPE, LEARN_INFO_DTYPE, NEIGH_IMAGE_INFO_DTYPE,
                      EGRESS_INFO_DTYPE, INGRESS_INFO_DTYPE, LAUNCH_INFO_DTYPE, NDP_DTYPE, RULE_DTYPE, RULE_INDEX_INFO_DTYPE,
                      RELEASE_INFO_DTYPE, RULE_STAT_DTYPE)
 
@@ -52,6 +52,7 @@ INGRESS_REF, INGRESS_WINDOW, INGRESS_FULL = 0, 1, 2   # UPE_INGRESS_REF / _WINDO
 LATENCY_BLOCK = 1024      # UPE_LATENCY_BLOCK: packets per workgroup pass of the histogram kernel
 CTRL_BLOCK = 1024         # UPE_CTRL_BLOCK: packets per workgroup of the control-write kernels
 PATCH_BLOCK = 256         # UPE_PATCH_BLOCK: records per workgroup of the neighbour-patch kernels
+LEARN_CHUNK = 1024        # UPE_LEARN_CHUNK: records per step of the neighbour-learn kernel
 RELEASE_BLOCK = 1024      # UPE_RELEASE_BLOCK: packets per workgroup of the release-order kernels
 
 
@@ -168,6 +169,8 @@ def _load() -> ctypes.CDLL:
         "upe_gpu_ctrl_writes": (I, [P, P, P, SZ, P, SZ, P, P]),
         "upe_gpu_process_segmented": (I, [P, P, P, P, SZ, P, SZ, P, SZ, ctypes.c_int64, P, P]),
         "upe_gpu_neigh_patch": (I, [P, P, SZ, P, P, P]),
+        "upe_gpu_neigh_learn": (I, [P, P, SZ, P, P, P]),
+        "upe_neigh_compile_room": (P, [P, SZ, P, SZ, SZ, SZ]),
         "upe_gpu_process_segmented_resident": (I, [P, P, P, P, SZ, P, SZ, P, SZ, ctypes.c_int64, P,
                                                    P]),
         "upe_gpu_release_order": (I, [P, P, SZ, P, SZ, ctypes.c_uint32, P, P, P, P, P, P, P]),
@@ -200,6 +203,8 @@ def _load() -> ctypes.CDLL:
         "upe_neigh_apply_writes": (I, [P, SZ, P, SZ, P, SZ, ctypes.c_int64, P]),
         "upe_neigh_patch_host": (I, [P, P, SZ, P, P]),
         "upe_neigh_image_lookup_host": (I, [P, P, SZ, P]),
+        "upe_neigh_learn_host": (I, [P, P, SZ, P, P]),
+        "upe_neigh_image_read": (I, [P, P, P, SZ, P, SZ]),
         "upe_release_order_host": (I, [P, SZ, P, SZ, ctypes.c_uint32, P, P, P, P, P, P]),
         "upe_release_flush": (I, [P, P, P, P, P, SZ, ctypes.c_uint32, SZ, P, P, SZ,
                                   ctypes.POINTER(ReleaseOps), P, P, P]),
@@ -255,6 +260,8 @@ EXPORTED = ("upe_gpu_last_error", "upe_gpu_device_count", "upe_gpu_local_cpus", 
             "upe_gpu_ctrl_writes", "upe_ctrl_writes_host", "upe_neigh_apply_writes",
             "upe_gpu_neigh_patch", "upe_neigh_patch_host", "upe_neigh_image_lookup_host",
             "upe_gpu_process_segmented_resident",
+            "upe_gpu_neigh_learn", "upe_neigh_learn_host", "upe_neigh_compile_room",
+            "upe_neigh_image_read",
             "upe_gpu_release_order", "upe_release_order_host", "upe_release_flush")
 
 
@@ -664,6 +671,16 @@ class GpuWorker:
                                        _dev_ptr(miss) or None, _dev_ptr(info) or None,
                                        stream or None), "upe_gpu_neigh_patch")
 
+    def neigh_learn(self, writes, count: int, defer, info, stream=None) -> None:
+        """upe_gpu_neigh_learn: the records applied to the loaded snapshot on the device, new
+        addresses included (neigh.learn is the same on the slot arrays plus the index,
+        neigh_learn_host on a NeighImage).  Device buffers: writes (count CTRL_WRITE_DTYPE records,
+        16-byte aligned), defer (count uint32 or None: the deferred records' ranks), info (64
+        bytes, LEARN_INFO_DTYPE)."""
+        _check(LIB.upe_gpu_neigh_learn(self._ctx, _dev_ptr(writes) or None, count,
+                                       _dev_ptr(defer) or None, _dev_ptr(info) or None,
+                                       stream or None), "upe_gpu_neigh_learn")
+
     # ---- release order ----
     def release_order(self, verdict, n: int, order, burst_fwd, info, first=None, nb: int = 0,
                       burst: int = 0, slot=None, handle=None, reply=None, stream=None) -> None:
@@ -875,6 +892,20 @@ def neigh_patch_host(image: "NeighImage", writes: np.ndarray):
     m = int(info["missed"][0])
     assert (miss[m:] == 0xEEEEEEEE).all(), "written past the missed ranks"
     return miss[:m].copy(), info[0]
+
+
+def neigh_learn_host(image: "NeighImage", writes: np.ndarray):
+    """upe_neigh_learn_host: the records applied to a compiled snapshot (in place), new addresses
+    included; (the deferred records' ranks, the LEARN_INFO_DTYPE record)."""
+    w = np.ascontiguousarray(writes, CTRL_WRITE_DTYPE)
+    defer = np.full(max(len(w), 1), 0xEEEEEEEE, np.uint32)
+    info = np.zeros(1, LEARN_INFO_DTYPE)
+    if LIB.upe_neigh_learn_host(image.ptr, _np_ptr(w) if len(w) else None, len(w), _np_ptr(defer),
+                                _np_ptr(info)) != 0:
+        raise UpeGpuError(f"upe_neigh_learn_host: {LIB.upe_gpu_last_error().decode()}")
+    d = int(info["deferred"][0])
+    assert (defer[d:] == 0xEEEEEEEE).all(), "written past the deferred ranks"
+    return defer[:d].copy(), info[0]
 
 
 def neigh_image_lookup_host(image: "NeighImage", keys: np.ndarray) -> np.ndarray:
@@ -1153,14 +1184,32 @@ class RuleImage:
 class NeighImage:
     """upe_neigh_compile: the neighbour snapshot of two slot arrays compiled for the GPU path on
     the host, with no context or GPU (where the tables change: after arp_expire / ndp_expire);
-    free() (or garbage collection) releases it."""
+    free() (or garbage collection) releases it.  room=(arp_room, ndp_room): upe_neigh_compile_room,
+    each index sized for that many more addresses (upe_gpu_neigh_learn)."""
 
-    def __init__(self, arp: np.ndarray | None, ndp: np.ndarray | None):
+    def __init__(self, arp: np.ndarray | None, ndp: np.ndarray | None, room=None):
         a, b = _neigh_tables(arp, ndp)
-        self.ptr = LIB.upe_neigh_compile(_np_ptr(a) if len(a) else None, len(a),
-                                         _np_ptr(b) if len(b) else None, len(b))
+        pa, pb = _np_ptr(a) if len(a) else None, _np_ptr(b) if len(b) else None
+        if room is None:
+            self.ptr = LIB.upe_neigh_compile(pa, len(a), pb, len(b))
+        else:
+            self.ptr = LIB.upe_neigh_compile_room(pa, len(a), pb, len(b), int(room[0]),
+                                                  int(room[1]))
         if not self.ptr:
             raise UpeGpuError(f"upe_neigh_compile: {LIB.upe_gpu_last_error().decode()}")
+
+    def read(self):
+        """upe_neigh_image_read: (info, arp_slots, ndp_slots) — the NEIGH_IMAGE_INFO_DTYPE record
+        and copies of the index slot arrays as uint32 words, (slots, 4) and (slots, 8)."""
+        info = np.zeros(1, NEIGH_IMAGE_INFO_DTYPE)
+        _check(LIB.upe_neigh_image_read(self.ptr, _np_ptr(info), None, 0, None, 0),
+               "upe_neigh_image_read")
+        na = 1 << int(info["arp_bits"][0]) if info["arp_bits"][0] else 1
+        nn = 1 << int(info["ndp_bits"][0]) if info["ndp_bits"][0] else 1
+        arp, ndp = np.zeros((na, 4), np.uint32), np.zeros((nn, 8), np.uint32)
+        _check(LIB.upe_neigh_image_read(self.ptr, None, _np_ptr(arp), arp.nbytes, _np_ptr(ndp),
+                                        ndp.nbytes), "upe_neigh_image_read")
+        return info[0], arp, ndp
 
     def free(self) -> None:
         if self.ptr:

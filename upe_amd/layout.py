@@ -80,6 +80,14 @@ PATCH_INFO_DTYPE = np.dtype([("records", "<u8"), ("patched", "<u8"), ("missed", 
                              ("first_miss", "<u8")])
 SEGMENT_INFO_DTYPE = np.dtype([("writes", "<u8"), ("patched", "<u8"), ("rebuilds", "<u8"),
                                ("ctrl", "<u8")])
+# upe_neigh_learn_info_t (upe_gpu_neigh_learn) and upe_neigh_image_info_t (upe_neigh_image_read)
+LEARN_INFO_DTYPE = np.dtype([("records", "<u8"), ("patched", "<u8"), ("inserted", "<u8"),
+                             ("dropped", "<u8"), ("deferred", "<u8"), ("first_defer", "<u8"),
+                             ("arp_free", "<u8"), ("ndp_free", "<u8")])
+NEIGH_IMAGE_INFO_DTYPE = np.dtype([("arp_bits", "<u4"), ("arp_seed", "<u4"), ("ndp_bits", "<u4"),
+                                   ("ndp_seed", "<u4"), ("arp_free", "<u4"), ("ndp_free", "<u4"),
+                                   ("arp_insertable", "<u4"), ("ndp_insertable", "<u4")])
+LEARN_CHUNK = 1024           # UPE_LEARN_CHUNK: records per step of upe_gpu_neigh_learn
 # upe_release_info_t (upe_gpu_release_order)
 RELEASE_INFO_DTYPE = np.dtype([("packets", "<u8"), ("bursts", "<u8"), ("forwarded", "<u8"),
                                ("consumed", "<u8"), ("dropped", "<u8"), ("replies", "<u8"),

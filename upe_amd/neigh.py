@@ -73,6 +73,109 @@ def resolve_keys(arp, ndp, keys) -> np.ndarray:
     return out
 
 
+_M32 = 0xFFFFFFFF
+
+
+def slots3(k: int, seed: int, bits: int):
+    """slot1 / slot2 / slot3 of csrc/upe_dev.h: an index key's three candidate slots."""
+    s1 = (((k ^ seed) * 0x9E3779B1) & _M32) >> (32 - bits)
+    x = ((k ^ seed) * 0x85EBCA77) & _M32
+    s2 = (((x ^ (x >> 16)) * 0xC2B2AE3D) & _M32) >> (32 - bits)
+    x = ((k ^ ((seed * 0x9E3779B9) & _M32)) * 0x27D4EB2F) & _M32
+    s3 = (((x ^ (x >> 15)) * 0x165667B1) & _M32) >> (32 - bits)
+    return s1, s2, s3
+
+
+def fold_v6(w) -> int:
+    """fold_v6 of csrc/upe_dev.h: the NDP index's key of an address's four little-endian words."""
+    return (((w[0] * 0x9E3779B1) & _M32) ^ ((w[1] * 0x85EBCA77) & _M32) ^
+            ((w[2] * 0xC2B2AE3D) & _M32) ^ ((w[3] * 0x27D4EB2F) & _M32))
+
+
+def _update(t, home: int, same, ip, mac) -> None:
+    """arp_update / ndp_update (reference src/arp_table.c:26-53, src/ndp_table.c:39-65): from the
+    home slot, the first slot that is invalid or holds the address takes it; a full table without
+    it is left alone.  update_at is not modelled."""
+    cap = len(t)
+    for j in range(cap):
+        s = (home + j) & (cap - 1)
+        if not t["valid"][s] or same(s):
+            t["ip"][s], t["mac"][s], t["valid"][s] = ip, mac, 1
+            return
+
+
+def learn(index, writes, arp=None, ndp=None):
+    """upe_gpu_neigh_learn restated: the contract's loop (include/upe_gpu.h) over the records
+    (CTRL_WRITE_DTYPE, in rank order) on the index — (info, arp_slots, ndp_slots) as
+    gpu.NeighImage.read() gives it: the NEIGH_IMAGE_INFO_DTYPE record and the slot arrays as uint32
+    words — and, where they are given, arp_update / ndp_update of every record that is not deferred
+    on the slot arrays the index was compiled from.  Returns (index, defer, info, arp, ndp): the
+    changed copies, the deferred ranks ascending (uint32) and (records, patched, inserted, dropped,
+    deferred, first_defer, arp_free, ndp_free), first_defer 2^64 - 1 where nothing is deferred."""
+    meta, aslots, nslots = index
+    meta, aslots, nslots = meta.copy(), aslots.copy(), nslots.copy()
+    arp = None if arp is None else np.asarray(arp, ARP_DTYPE).copy()
+    ndp = None if ndp is None else np.asarray(ndp, NDP_DTYPE).copy()
+    w = np.asarray(writes).ravel()
+    free = {4: int(meta["arp_free"]), 6: int(meta["ndp_free"])}
+    counts = [0, 0, 0]   # patched, inserted, dropped
+    defer = []
+    for r in range(len(w)):
+        kind = int(w["kind"][r])
+        if kind not in (4, 6):
+            defer.append(r)
+            continue
+        v6 = kind == 6
+        fam = "ndp" if v6 else "arp"
+        bits, seed = int(meta[fam + "_bits"]), int(meta[fam + "_seed"])
+        slots = nslots if v6 else aslots
+        words = [int(x) for x in np.frombuffer(w["ip"][r].tobytes(), "<u4")]
+        if not v6:
+            words = words[:1]
+        mac = w["mac"][r].tobytes()
+        lo, hi = int.from_bytes(mac[:4], "little"), int.from_bytes(mac[4:], "little")
+        used_at, mac_at = (5, 4) if v6 else (2, 1)   # the word with the used bit; the MAC's first
+        cand = slots3(fold_v6(words) if v6 else words[0], seed, bits) if bits else ()
+        hit = [c for c in cand if (slots[c, used_at] >> 16) & 1 and
+               [int(x) for x in slots[c, :len(words)]] == words]
+        outcome = None
+        if hit:
+            c = hit[0]
+            slots[c, mac_at] = lo
+            slots[c, mac_at + 1] = (int(slots[c, mac_at + 1]) & 0xFFFF0000) | hi
+            outcome = 0
+        elif not int(meta[fam + "_insertable"]):
+            defer.append(r)
+        elif free[kind] == 0:
+            outcome = 2
+        else:
+            room = [c for c in cand if not (slots[c, used_at] >> 16) & 1]
+            if not room:
+                defer.append(r)
+            else:
+                slots[room[0]] = 0
+                slots[room[0], :len(words)] = words
+                slots[room[0], mac_at] = lo
+                slots[room[0], mac_at + 1] = hi | 1 << 16
+                free[kind] -= 1
+                outcome = 1
+        if outcome is None:
+            continue
+        counts[outcome] += 1
+        t = ndp if v6 else arp
+        if t is not None and len(t):
+            ip = w["ip"][r] if v6 else words[0]
+            if v6:
+                x = words[0] ^ words[1] ^ words[2] ^ words[3]
+                _update(t, x, lambda s: t["ip"][s].tobytes() == w["ip"][r].tobytes(), ip, w["mac"][r])
+            else:
+                _update(t, words[0], lambda s: int(t["ip"][s]) == words[0], ip, w["mac"][r])
+    meta["arp_free"], meta["ndp_free"] = free[4], free[6]
+    first = defer[0] if defer else (1 << 64) - 1
+    info = (len(w), counts[0], counts[1], counts[2], len(defer), first, free[4], free[6])
+    return (meta, aslots, nslots), np.asarray(defer, np.uint32), info, arp, ndp
+
+
 def patch(arp, ndp, writes):
     """upe_gpu_neigh_patch restated on the slot arrays: the records (CTRL_WRITE_DTYPE, in rank
     order) whose address the probe above reaches before the batch — arp_get_mac of ip bytes 0-3 for
