@@ -898,7 +898,10 @@ int upe_tx_flush_packed(const uint8_t *h_out, const uint64_t *h_out_desc,
  * are powers of two, as arp_table_init / ndp_table_init require.  The NS/NA option walk reads
  * the whole frame (len bytes), so this call needs FULL frames: a batch of UPE_FRAME_TAIL-byte
  * header windows (upe_gpu_process_host's window form) is not valid here — an NS/NA longer than
- * its window would have its options read from the bytes that follow the window. */
+ * its window would have its options read from the bytes that follow the window.  When the
+ * upe_gpu_load_neigh of a table write fails, the call (and upe_gpu_process_segmented_resident)
+ * returns -1 with that call's message and the snapshot loaded before the write stays loaded;
+ * nothing is promised about the outputs of the partly processed batch. */
 int upe_gpu_process_segmented(upe_gpu_ctx_t *ctx, uint8_t *d_frames, const uint64_t *d_desc,
                               uint32_t *d_verdict, size_t n, upe_arp_entry_t *arp,
                               size_t arp_capacity, upe_ndp_entry_t *ndp, size_t ndp_capacity,
